@@ -20,9 +20,19 @@ Workloads (BASELINE.json configs):
      protein rows row-split (strong scaling, sharding.py).
   D (configs[4]): d = 256 bf16 DEDICOM scoring of every drug-drug slot's 512 + 512 pairs.
 
-The default line (config S) also carries a "P" block (config P's forward step, the staged
-SpMM's roofline, its CPU baseline) and a "D" block (config 5's scorer), at every N, so the
-driver's own runs record every north-star number; --no-extra drops them.
+A plain run sets up, warms up, times the steps and prints the line: value, ms_per_step and the
+workload's description.  --full adds everything measured in runs of their own: the dominant
+kernel's roofline and each SpMM launch timed alone, the device-side timing split, the CPU
+baseline and, for config S, a "P" block (config P's forward step, the staged SpMM's roofline,
+its CPU baseline) and a "D" block (config 5's scorer), at every N, so one run records every
+north-star number (--no-extra / --no-cpu-baseline drop those parts of it); at N > 1 also the
+phase times and the peer-store step beside the RCCL one.
+
+--dump-outputs DIR writes what the last timed step computed (the arrays a caller of the timed
+path receives: hidden layer, embeddings, decoder scores, sampled negatives, loss) as
+DIR/<name>.npy, float32 (integers as float64); an array that would take the total past 64 MB
+is written as a fixed seeded sample of its elements.  Inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 Prints one JSON line (rank 0).
 """
@@ -59,10 +69,17 @@ def parse(argv=None):
                     help="S / P: the GCN forward step (metric: edges/s); D: config 5, bf16 DEDICOM "
                          "scoring of every drug-drug slot's batch (metric: scored pairs/s)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a hipGraph")
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU baseline time budget per form")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the dominant kernel's roofline and every SpMM launch "
+                         "timed alone, the device-side timing split, the CPU baseline, config S's P / D "
+                         "blocks, and at N > 1 the phase times and the peer-store step beside RCCL")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (embeddings, "
+                         "decoder scores, loss) as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="--full: CPU baseline time budget per form")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: omit the CPU baseline")
     ap.add_argument("--no-extra", action="store_true",
-                    help="config S: omit the P / D blocks of the default line")
+                    help="--full, config S: omit the P / D blocks of the line")
     ap.add_argument("--p-steps", type=int, default=100, help="timed steps of the P block")
     ap.add_argument("--d-steps", type=int, default=100, help="timed steps of the D block")
     ap.add_argument("--kernel-reps", type=int, default=200)
@@ -96,8 +113,8 @@ def parse(argv=None):
     ap.add_argument("--exchange", choices=["rccl", "peer", "peer-kernel"], default="rccl",
                     help="N > 1 (and --simulate-world): the row-split blocks' all-gather over RCCL, or by peer "
                          "stores over xGMI (peer.py) fused into the finishing launches (peer) or as a "
-                         "stand-alone launch (peer-kernel); the line's \"peer\" block times the peer form "
-                         "beside the RCCL default at N > 1 either way")
+                         "stand-alone launch (peer-kernel); with --full the line's \"peer\" block times the "
+                         "peer form beside the RCCL default at N > 1 either way")
     return ap.parse_args(argv)
 
 
@@ -251,7 +268,41 @@ def time_kernel(fn, reps, stream):
 
 
 WARM_REPLAYS = knob("DG_WARM_REPLAYS", 1)  # untimed replays after capture
-LAST_TIMING = {}  # timed_steps: the last timed region's device-side span (HIP events), untimed rerun
+FULL = False  # --full (set by main)
+LAST_TIMING = {}  # timed_steps, --full: the last timed region's device-side span (HIP events), untimed rerun
+DUMP_BUDGET = 48 << 20  # --dump-outputs: bytes of .npy data in all (the limit is 64 MB)
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: each array as directory/<name>.npy, float32 (other dtypes as float64).
+    Past DUMP_BUDGET in all, every array above an equal share is cut to a sorted sample of its
+    flattened elements drawn with a fixed seed (the same elements on every run)."""
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET:
+        share = DUMP_BUDGET // len(arrays)
+        for k, a in arrays.items():
+            if a.nbytes > share:
+                pick = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+                arrays[k] = a.reshape(-1)[np.sort(pick)]
+    for k, a in arrays.items():
+        np.save(out / f"{k}.npy", a)
+
+
+def step_outputs(plan, dec):
+    """What a caller of the forward step receives: both layers' outputs per node type and the
+    decoder's scores, sampled negatives and loss."""
+    out = {}
+    for t, h in plan.hidden1.items():
+        out[f"hidden1_{t}"] = h.cpu().numpy()
+    for t, e in plan.embeddings.items():
+        out[f"embeddings_{t}"] = e.cpu().numpy()
+    f = dec.fused
+    out.update({"decoder_pos": f.pos.cpu().numpy(), "decoder_neg": f.neg.cpu().numpy(),
+                "decoder_neg_rows": f.neg_rows.cpu().numpy(), "loss": f.loss.cpu().numpy()})
+    return out
 
 
 def timed_steps(step, steps, warmup, G, stream, use_graph=True, barrier=None):
@@ -287,9 +338,12 @@ def timed_steps(step, steps, warmup, G, stream, use_graph=True, barrier=None):
         if barrier:
             barrier()
         el = time.perf_counter() - t0
-        # (untimed) the same replays once more between HIP events on the stream: the device's
-        # own span, against which the wall-clock figure above shows the host's launch and
-        # completion-wait cost of the timed region
+        LAST_TIMING.clear()
+        if not FULL:
+            return el
+        # (untimed, --full) the same replays once more between HIP events on the stream: the
+        # device's own span, against which the wall-clock figure above shows the host's launch
+        # and completion-wait cost of the timed region
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(stream)
         h0 = time.perf_counter()
@@ -298,7 +352,6 @@ def timed_steps(step, steps, warmup, G, stream, use_graph=True, barrier=None):
         h1 = time.perf_counter()
         e1.record(stream)
         e1.synchronize()
-        LAST_TIMING.clear()
         LAST_TIMING.update({"device_ms_per_step": e0.elapsed_time(e1) / steps,
                             "host_enqueue_ms": (h1 - h0) * 1e3, "wall_ms_per_step": el * 1e3 / steps})
         return el
@@ -366,10 +419,53 @@ def cpu_baseline(graph, seconds):
         return cb.measure(graph, H1, H2, seconds)
 
 
+def kernel_figures(plan, dg, config, world, kernel_reps, stream):
+    """--full: the roofline and per-layer SpMM fields of a forward record, each launch timed
+    alone (time_kernel)."""
+    # the roofline covers the dominant kernel: the longest SpMM launch of either layer (config
+    # S: layer 2's fused, reassociated launch; config P: layer 1's staged drug x drug SpMM), its
+    # algorithmic bytes over its own duration; each whole layer's SpMM (launches as the forward
+    # runs them) is reported beside it
+    l1, l2 = plan.spmm_launches
+    per = [(time_kernel(lambda l=l: l(), kernel_reps, stream), 1, i) for i, l in enumerate(l1)]
+    per += [(time_kernel(lambda l=l: l(), kernel_reps, stream), 2, i) for i, l in enumerate(l2)]
+    k_ms, dom_layer, di = max(per)
+    dom = (l1 if dom_layer == 1 else l2)[di]
+    dom_d = H1 if dom_layer == 1 else H2
+    k_bytes = plan.launch_bytes(dom, dom_layer)
+    achieved = k_bytes / (k_ms * 1e-3) / 1e9
+    l1_ms = time_kernel(plan._layer1.run_spmm, kernel_reps, stream)
+    l1_bytes = plan.layer_bytes(1)
+    k2_ms = time_kernel(plan._layer2.run_spmm, kernel_reps, stream)
+    l2_bytes = plan.layer_bytes(2)
+    traffic, traffic_src, traffic_ms = pmc_traffic(config if world == 1 else None, dom, dom_d, dom_layer)
+    return {
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                     "traffic_source": traffic_src, "traffic_profiled_kernel_ms": traffic_ms,
+                     "kernel": _kernel_label(dom, dom_d) + f" (layer {dom_layer})",
+                     "kernel_ms": k_ms, "algorithmic_bytes": k_bytes,
+                     "launches_us": {f"layer{ly} {_kernel_label((l1 if ly == 1 else l2)[i], H1 if ly == 1 else H2)}":
+                                     ms * 1e3 for ms, ly, i in per}},
+        "spmm_layer1": {"launches": [type(x).__name__ for x in l1], "ms": l1_ms,
+                        "algorithmic_bytes": l1_bytes, "GB_s": l1_bytes / (l1_ms * 1e-3) / 1e9,
+                        "frac": l1_bytes / (l1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        "edges_per_s": dg.total_nnz / (l1_ms * 1e-3)},
+        # layer 2's compulsory bytes: the CSR once, H1_j (reassociated / staged forms) or P_k
+        # once, W2 once where the launch reads it, the output once (ForwardPlan.layer_bytes)
+        "spmm_layer2": {"launches": [type(x).__name__ for x in l2], "ms": k2_ms,
+                        "algorithmic_bytes": l2_bytes, "GB_s": l2_bytes / (k2_ms * 1e-3) / 1e9,
+                        "frac": l2_bytes / (k2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                        "edges_per_s": dg.total_nnz / (k2_ms * 1e-3)},
+        "spmm_layer2_ms": k2_ms,
+    }
+
+
 # ----------------------------------------------------------------------------- forward step
-def forward_bench(args, config, rank, world, sharded, device, dist, steps, warmup, kernel_reps):
-    """One config's forward step: value (edges/s over every rank), the dominant layer-1
-    kernel's roofline, the whole layer-1 SpMM.  Returns (record fields, graph)."""
+def forward_bench(args, config, rank, world, sharded, device, dist, steps, warmup, kernel_reps, dump=None):
+    """One config's forward step: value (edges/s over every rank) and, with --full, the
+    dominant kernel's roofline and each layer's whole SpMM.  `dump`: the --dump-outputs
+    directory (rank 0 writes the last timed step's outputs).  Returns (record fields, graph)."""
     import torch
 
     graph, shard, scaling, workload = build_workload(config, rank, world, sharded, args.backend, args.exchange)
@@ -440,23 +536,6 @@ def forward_bench(args, config, rank, world, sharded, device, dist, steps, warmu
         el_max, tot_edges = float(tm[0]), float(t[1])
     value = tot_edges * steps / el_max
 
-    # the roofline covers the dominant kernel: the longest SpMM launch of either layer (config
-    # S: layer 2's fused, reassociated launch; config P: layer 1's staged drug x drug SpMM), its
-    # algorithmic bytes over its own duration; each whole layer's SpMM (launches as the forward
-    # runs them) is reported beside it
-    l1, l2 = plan.spmm_launches
-    per = [(time_kernel(lambda l=l: l(), kernel_reps, stream), 1, i) for i, l in enumerate(l1)]
-    per += [(time_kernel(lambda l=l: l(), kernel_reps, stream), 2, i) for i, l in enumerate(l2)]
-    k_ms, dom_layer, di = max(per)
-    dom = (l1 if dom_layer == 1 else l2)[di]
-    dom_d = H1 if dom_layer == 1 else H2
-    k_bytes = plan.launch_bytes(dom, dom_layer)
-    achieved = k_bytes / (k_ms * 1e-3) / 1e9
-    l1_ms = time_kernel(plan._layer1.run_spmm, kernel_reps, stream)
-    l1_bytes = plan.layer_bytes(1)
-    k2_ms = time_kernel(plan._layer2.run_spmm, kernel_reps, stream)
-    l2_bytes = plan.layer_bytes(2)
-    traffic, traffic_src, traffic_ms = pmc_traffic(config if world == 1 else None, dom, dom_d, dom_layer)
     rec = {
         "value": value,
         "unit": "edges/s",
@@ -464,40 +543,27 @@ def forward_bench(args, config, rank, world, sharded, device, dist, steps, warmu
         "steps": steps,
         "warmup": warmup,
         "ms_per_step": el_max * 1e3 / steps,
-        "timing_split": split,
         "scaling": scaling,
         "config": {"workload": workload, "nnz_per_layer_total": int(tot_edges // 2),
                    "parallelism": (plan.parallelism(args.backend) if sharded else "1 GPU"),
                    "hipgraph": use_graph, "launch": mode, "steps_per_graph": G},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "traffic_source": traffic_src, "traffic_profiled_kernel_ms": traffic_ms,
-                     "kernel": _kernel_label(dom, dom_d) + f" (layer {dom_layer})",
-                     "kernel_ms": k_ms, "algorithmic_bytes": k_bytes,
-                     "launches_us": {f"layer{ly} {_kernel_label((l1 if ly == 1 else l2)[i], H1 if ly == 1 else H2)}":
-                                     ms * 1e3 for ms, ly, i in per}},
-        "spmm_layer1": {"launches": [type(x).__name__ for x in l1], "ms": l1_ms,
-                        "algorithmic_bytes": l1_bytes, "GB_s": l1_bytes / (l1_ms * 1e-3) / 1e9,
-                        "frac": l1_bytes / (l1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                        "edges_per_s": dg.total_nnz / (l1_ms * 1e-3)},
-        # layer 2's compulsory bytes: the CSR once, H1_j (reassociated / staged forms) or P_k
-        # once, W2 once where the launch reads it, the output once (ForwardPlan.layer_bytes)
-        "spmm_layer2": {"launches": [type(x).__name__ for x in l2], "ms": k2_ms,
-                        "algorithmic_bytes": l2_bytes, "GB_s": l2_bytes / (k2_ms * 1e-3) / 1e9,
-                        "frac": l2_bytes / (k2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                        "edges_per_s": dg.total_nnz / (k2_ms * 1e-3)},
-        "spmm_layer2_ms": k2_ms,
     }
+    if dump is not None and rank == 0:
+        dump_outputs(dump, step_outputs(plan, dec))
+    if FULL:
+        rec["timing_split"] = split
+        rec.update(kernel_figures(plan, dg, config, world, kernel_reps, stream))
     if sharded:
         rec["rank_ms_per_step"] = el * 1e3 / steps
         if plan.peer is not None:
             rec["peer_error_word"] = plan.peer.error()
-        if args.backend == "nccl" and use_graph:
+        if FULL and args.backend == "nccl" and use_graph:
             rec["phases"] = phase_times(plan, dec, stream, dist, min(kernel_reps, 20))
-        if plan.xregion is not None and use_graph:
+        if FULL and plan.xregion is not None and use_graph:
             rec["peer_probe"] = peer_probe(plan, stream, dist, min(kernel_reps, 20), rank, world)
-        rec["_outputs"] = [{t: h.cpu().numpy() for t, h in plan.hidden1.items()},
-                           {t: e.cpu().numpy() for t, e in plan.embeddings.items()}]
+        if FULL:  # (the peer-store step of main() is checked against these)
+            rec["_outputs"] = [{t: h.cpu().numpy() for t, h in plan.hidden1.items()},
+                               {t: e.cpu().numpy() for t, e in plan.embeddings.items()}]
         if plan.peer is not None:
             dist.barrier()
             plan.peer.close()
@@ -626,8 +692,32 @@ def peer_step(args, rank, world, device, dist, steps, warmup, ref_outputs, confi
     return rec
 
 
+def scorer_roofline(args, sc, steps, stream, d):
+    """--full: config 5's roofline block, the step's one launch timed alone."""
+    from decagon_amd import kernels
+
+    reps = args.kernel_reps if steps >= 50 else 20
+    # the step's one launch (sampler + scores + hinge: dg_slot_score_hinge_bf16), alone
+    k_ms = time_kernel(lambda: kernels.slot_score_hinge_bf16(
+        sc.E_row, sc.E_col, sc.rows[:sc.n], sc.cols[:sc.n], sc.alias, sc.s0, sc.s1 - sc.s0, sc.batch, sc.seed, sc.R,
+        sc.D, sc.margin, sc.out, sc.neg_rows, sc.loss, sc._ws), reps, stream)
+    # flops the column-shared paired kernel issues per (positive, negative) pair: T = R·(D_k∘v)
+    # on the MFMA (2d²) once for both, the B operand (d) and two dots with u∘D_k (2·3d) on the
+    # VALU — against 2·(2d² + 4d) when each pair is contracted on its own
+    flop_pp = 2 * d * d + 7 * d
+    n = 2 * sc.n
+    tflops = sc.n * flop_pp / (k_ms * 1e-3) / 1e12
+    mfma_tflops = sc.n * 2 * d * d / (k_ms * 1e-3) / 1e12
+    return {"bound": "mfma", "achieved": tflops, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": tflops / BF16_PEAK_TFLOPS, "traffic": None,
+            "kernel": "decoder_bf16_cs16_kernel<768, true> (sampler + scores + hinge)",
+            "kernel_ms": k_ms,
+            "algorithmic_flops": sc.n * flop_pp, "mfma_tflops": mfma_tflops,
+            "per_pair_form_tflops": n * (2 * d * d + 4 * d) / (k_ms * 1e-3) / 1e12}
+
+
 # ----------------------------------------------------------------------------- config 5
-def decoder_bench(args, device, steps, warmup, rank=0, world=1, dist=None):
+def decoder_bench(args, device, steps, warmup, rank=0, world=1, dist=None, dump=None):
     """Config 5 (BASELINE configs[4]): d = 256 bf16 embeddings / R / D_k, DEDICOM decoder on
     MFMA, every one of the 1,928 drug-drug relation slots scoring B = 512 positives and 512
     negatives drawn on the device from THAT slot's degree^0.75 alias table, then the hinge loss
@@ -658,19 +748,10 @@ def decoder_bench(args, device, steps, warmup, rank=0, world=1, dist=None):
         t = torch.tensor([el], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t[0])
-    reps = args.kernel_reps if steps >= 50 else 20
-    # the step's one launch (sampler + scores + hinge: dg_slot_score_hinge_bf16), alone
-    k_ms = time_kernel(lambda: kernels.slot_score_hinge_bf16(
-        sc.E_row, sc.E_col, sc.rows[:sc.n], sc.cols[:sc.n], sc.alias, sc.s0, sc.s1 - sc.s0, sc.batch, sc.seed, sc.R,
-        sc.D, sc.margin, sc.out, sc.neg_rows, sc.loss, sc._ws), reps, stream)
-    # flops the column-shared paired kernel issues per (positive, negative) pair: T = R·(D_k∘v)
-    # on the MFMA (2d²) once for both, the B operand (d) and two dots with u∘D_k (2·3d) on the
-    # VALU — against 2·(2d² + 4d) when each pair is contracted on its own
-    flop_pp = 2 * d * d + 7 * d
-    n = 2 * sc.n
-    tflops = sc.n * flop_pp / (k_ms * 1e-3) / 1e12
-    mfma_tflops = sc.n * 2 * d * d / (k_ms * 1e-3) / 1e12
-    return {
+    if dump is not None and rank == 0:
+        dump_outputs(dump, {"scores_pos": sc.pos.cpu().numpy(), "scores_neg": sc.neg.cpu().numpy(),
+                            "neg_rows": sc.neg_rows.cpu().numpy(), "loss": sc.loss.cpu().numpy()})
+    rec = {
         "metric": "DEDICOM scored pairs/sec (config 5: d=256 bf16, all 1,928 drug-drug slots)",
         "value": 2 * slots * B * steps / el,
         "unit": "pairs/s",
@@ -678,7 +759,6 @@ def decoder_bench(args, device, steps, warmup, rank=0, world=1, dist=None):
         "steps": steps,
         "warmup": warmup,
         "ms_per_step": el * 1e3 / steps,
-        "timing_split": dict(LAST_TIMING),
         "scaling": "strong",
         "dtype": "bf16 (fp32 accumulation)",
         "data": "synthetic: per-slot relations (Zipf sizes, SURVEY §8d), positives = slot edges, negatives "
@@ -688,13 +768,11 @@ def decoder_bench(args, device, steps, warmup, rank=0, world=1, dist=None):
                    "pairs_per_step": 2 * slots * B, "slots_this_rank": s1 - s0, "hipgraph": not args.no_graph,
                    "steps_per_graph": G},
         "loss": float(sc.loss[0]),
-        "roofline": {"bound": "mfma", "achieved": tflops, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": tflops / BF16_PEAK_TFLOPS, "traffic": None,
-                     "kernel": "decoder_bf16_cs16_kernel<768, true> (sampler + scores + hinge)",
-                     "kernel_ms": k_ms,
-                     "algorithmic_flops": sc.n * flop_pp, "mfma_tflops": mfma_tflops,
-                     "per_pair_form_tflops": n * (2 * d * d + 4 * d) / (k_ms * 1e-3) / 1e12},
     }
+    if FULL:
+        rec["timing_split"] = dict(LAST_TIMING)
+        rec["roofline"] = scorer_roofline(args, sc, steps, stream, d)
+    return rec
 
 
 def main_decoder(args):
@@ -708,7 +786,7 @@ def main_decoder(args):
         ranks = []
         for r in (range(N) if args.simulate_rank < 0 else [args.simulate_rank]):
             x = decoder_bench(args, torch.device("cuda", 0), args.steps, args.warmup, r, N, None)
-            ranks.append({"rank": r, "ms_per_step": x["ms_per_step"], "kernel_ms": x["roofline"]["kernel_ms"],
+            ranks.append({"rank": r, "ms_per_step": x["ms_per_step"], "kernel_ms": x.get("roofline", {}).get("kernel_ms"),  # (--full)
                           "slots": x["config"]["slots_this_rank"]})
             print(f"rank {r}/{N}: {ranks[-1]['ms_per_step'] * 1e3:.1f} us/step", file=sys.stderr, flush=True)
         rec = {"metric": "config D sharded-step rehearsal on one GPU (the loss all-reduce not run)", "world": N,
@@ -717,7 +795,7 @@ def main_decoder(args):
                "policy_overrides": overrides()}
         print(json.dumps(rec), file=JSON_OUT, flush=True)
         return
-    rec = decoder_bench(args, torch.device("cuda", 0), args.steps, args.warmup)
+    rec = decoder_bench(args, torch.device("cuda", 0), args.steps, args.warmup, dump=args.dump_outputs)
     rec.update({"higher_is_better": True, "vs_baseline": None, "cpu_baseline": None})
     rec["policy_overrides"] = overrides()  # DG_* knobs that differed from the defaults
     print(json.dumps(rec), file=JSON_OUT, flush=True)
@@ -794,6 +872,11 @@ def main_train(args):
     el = timed_steps(step, args.steps, max(0, args.warmup - 1), G, stream, not args.no_graph,
                      dist.barrier if sharded else None)
     loss1 = float(f.loss[0])
+    if args.dump_outputs is not None and rank == 0:
+        # the step's outputs and the variables it updated (the stacked weights per edge type)
+        out = step_outputs(plan, dec)
+        out.update({f"param_{i}": p.detach().float().cpu().numpy() for i, p in enumerate(params)})
+        dump_outputs(args.dump_outputs, out)
     params_n = int(sum(p.numel() for p in params))
     edges = 2 * dg.total_nnz
     if sharded:
@@ -906,7 +989,8 @@ def main():
     args = parse()
     # stdout carries exactly one JSON line: libraries that print to fd 1 (RCCL prints its
     # version banner at communicator init) are sent to stderr instead
-    global JSON_OUT
+    global JSON_OUT, FULL
+    FULL = args.full
     JSON_OUT = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
     if args.config == "D":
@@ -934,16 +1018,16 @@ def main():
             dist.init_process_group(args.backend)
 
     rec, graph = forward_bench(args, args.config, rank, world, sharded, device, dist, args.steps, args.warmup,
-                               args.kernel_reps)
+                               args.kernel_reps, dump=args.dump_outputs)
     ref_outputs = rec.pop("_outputs", None)
-    if sharded and args.config == "S" and args.exchange == "rccl" and args.backend == "nccl":
+    if FULL and sharded and args.config == "S" and args.exchange == "rccl" and args.backend == "nccl":
         # the peer-store form of the same step beside the RCCL default
         rec["peer"] = peer_step(args, rank, world, device, dist, args.steps, args.warmup, ref_outputs)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if FULL and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(graph, args.cpu_seconds)
     extra = {}
-    if args.config == "S" and not args.no_extra:
+    if FULL and args.config == "S" and not args.no_extra:
         # config P's forward step (configs[2]; sharded over the same ranks: configs[3]) and
         # config 5's scorer (configs[4]; slot-sharded) — the north-star numbers, on the
         # driver's own run

@@ -15,7 +15,7 @@ for rep in $(seq 1 ${REPS:-2}); do
     case $v in base) ;; *@*) lib=$PWD/decagon_amd/lib/var_${v%%@*}.so; envs=$(echo "${v#*@}" | tr ',' ' ');;
       *=*) envs=$(echo "$v" | tr ',' ' ');; *) lib=$PWD/decagon_amd/lib/var_$v.so;; esac
     name=$(echo "$v" | tr -c 'A-Za-z0-9_.-' '_')
-    env DG_LIB=$lib $envs timeout -k 10 300 python bench.py $args > $out/${name}_$rep.json 2> $out/${name}_$rep.err || exit $?
+    env DG_LIB=$lib $envs timeout -k 10 300 python bench.py --full $args > $out/${name}_$rep.json 2> $out/${name}_$rep.err || exit $?
     python scripts/bench_summary.py "$v" $out/${name}_$rep.json
   done
 done

@@ -10,7 +10,7 @@ grep -oE "^[[:space:]]*(TA|TD|TCP)_[A-Z_]+(BUSY|STALL)[A-Za-z_]*" $out/counters.
 run() {  # name, counters...
   local name=$1; shift
   timeout -s KILL 120 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $out/$name -o run -- \
-    python3 bench.py --config D --no-graph --steps 3 --warmup 1 --kernel-reps 3 > /dev/null 2> $out/$name.log
+    python3 bench.py --full --config D --no-graph --steps 3 --warmup 1 --kernel-reps 3 > /dev/null 2> $out/$name.log
   echo "$name rc=$?"
 }
 run sq SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_LDS

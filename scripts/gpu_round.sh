@@ -13,5 +13,5 @@ tail -1 $out/pytest.log
 case $rc in 0|1) ;; *) echo "pytest rc=$rc: stopping"; exit $rc;; esac
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { tail -5 $out/smoke.log; exit 1; }
 tail -1 $out/smoke.log
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || { tail -5 $out/bench.err; exit 1; }
 python scripts/bench_summary.py default $out/bench.json

@@ -10,7 +10,7 @@ n=0
 for set in "$@"; do
   n=$((n+1))
   timeout -k 10 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $out/s$n -o run -- \
-    python3 bench.py ${BENCH_ARGS:---config P} --no-graph --steps 2 --warmup 1 --kernel-reps 1 --no-cpu-baseline > /dev/null 2> $out/s$n.log || echo "pmc set $n failed"
+    python3 bench.py --full ${BENCH_ARGS:---config P} --no-graph --steps 2 --warmup 1 --kernel-reps 1 --no-cpu-baseline > /dev/null 2> $out/s$n.log || echo "pmc set $n failed"
 done
 python3 - "$out" "$filt" <<'PY'
 import csv, glob, sys, collections

@@ -27,19 +27,19 @@ for step in "$@"; do
     test) env $envs timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -k "$a" --timeout 400 \
             --timeout-method thread > $out/$name.log 2>&1 || { tail -30 $out/$name.log; exit 1; }
           tail -1 $out/$name.log; continue;;
-    bench) run python bench.py --config $a --steps 50 --warmup 5 || exit $?;;
+    bench) run python bench.py --full --config $a --steps 50 --warmup 5 || exit $?;;
     sim) run python bench.py --config $a --simulate-world $b --steps 100 --warmup 10 || exit $?
          python3 -c "import json; r=json.load(open('$out/$name.json')); print('$step', 'max', round(r['max_rank_ms_per_step']*1e3,2), 'us', [round(x['ms_per_step']*1e3,1) for x in r['ranks']])"
          continue;;
     prof) sim=""; [ "$b" -gt 1 ] && sim="--simulate-world $b --simulate-rank 0"
           cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
           env $envs timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$a$b -o run -- \
-            python3 bench.py --config $a $sim --steps 100 --warmup 10 --no-extra --no-cpu-baseline \
+            python3 bench.py --full --config $a $sim --steps 100 --warmup 10 --no-extra --no-cpu-baseline \
             > $out/$name.json 2> $out/$name.err || exit $?
           python3 scripts/trace_table.py $out/prof_$a$b | head -20; continue;;
     rccl) port=$((port + 1))
           run python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-            --master-port $port bench.py --config $a --force-shard --steps 20 --warmup 3 --no-cpu-baseline || exit $?;;
+            --master-port $port bench.py --full --config $a --force-shard --steps 20 --warmup 3 --no-cpu-baseline || exit $?;;
     train) run python bench.py --train --config $a --steps 10 --warmup 2 || exit $?;;
     trainrccl) port=$((port + 1))
           run python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \

@@ -6,7 +6,7 @@ tag=$1; cfg=$2; shift 2
 out=gpurun_out/$tag; mkdir -p $out
 for sg in $1; do
   s=${sg%%:*}; g=${sg##*:}
-  timeout -k 10 300 python bench.py --config $cfg --steps $s --warmup 5 --graph-steps $g --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --config $cfg --steps $s --warmup 5 --graph-steps $g --no-cpu-baseline \
     > $out/${cfg}_${s}_${g}.json 2> $out/${cfg}_${s}_${g}.err || exit $?
   python scripts/bench_summary.py "$cfg steps=$s graph=$g" $out/${cfg}_${s}_${g}.json
 done

@@ -18,8 +18,11 @@ Fixtures:
   dedicom_kat.npz   the reference's trained DEDICOM parameters (ndarray-dumpGlobalRelations.npy,
                     ndarray-dumpEmbeddingImportance.npyz.npz arr_0) with seeded embeddings and
                     the NpPredictor formula's scores (main/Predictor/NpPredictor.py:304).
+  apk_reference.npz seeded rankings and the AP@k the reference's rank_metrics.apk returns for
+                    them (decagon/utility/rank_metrics.py).
 
-Usage:  python tests/golden/make_golden.py
+Usage:  python tests/golden/make_golden.py          (every fixture)
+        python tests/golden/make_golden.py apk      (apk_reference.npz alone)
 """
 from __future__ import annotations
 
@@ -206,5 +209,41 @@ def main():
           {f"{i}{j}{k}": len(out[f'adj_{i}_{j}_{k}_values']) for (i, j) in et_list for k in range(edge_types[i, j])})
 
 
+APK_CASES = ((100, 50), (30, 50), (500, 10))  # (n scored items, k)
+
+
+def apk_inputs():
+    """The (scores, actual, predicted, k) of each AP@k case: seeded integer scores with ties,
+    the first third of the items relevant, the ranking by stable descending sort (as
+    tests/test_cpu_train_oracle.py::test_apk_restatement_matches_reference draws them)."""
+    rng = np.random.default_rng(4)
+    for n, k in APK_CASES:
+        scores = rng.integers(0, 15, n).astype(float)
+        actual = list(range(n // 3))
+        predicted = [i for _, i in sorted(zip(scores.tolist(), range(n)), reverse=True, key=lambda t: t[0])]
+        yield scores, actual, predicted, k
+
+
+def apk_fixture():
+    """apk_reference.npz: the reference's own rank_metrics.apk (decagon/utility/rank_metrics.py,
+    numpy-only) on the seeded cases of apk_inputs — the scores and the value it returned."""
+    spec = importlib.util.spec_from_file_location("ref_rank_metrics", REF / "decagon/utility/rank_metrics.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    out = {"cases": np.array(APK_CASES, dtype=np.int64)}
+    expected = []
+    for i, (scores, actual, predicted, k) in enumerate(apk_inputs()):
+        out[f"scores_{i}"] = scores
+        expected.append(mod.apk(actual, predicted, k))
+    out["expected"] = np.array(expected, dtype=np.float64)
+    np.savez_compressed(HERE / "apk_reference.npz", **out)
+    print("wrote", HERE / "apk_reference.npz", expected)
+
+
 if __name__ == "__main__":
-    main()
+    # python tests/golden/make_golden.py [apk]: every fixture, or apk_reference.npz alone
+    if sys.argv[1:] == ["apk"]:
+        apk_fixture()
+    else:
+        main()
+        apk_fixture()

@@ -612,3 +612,35 @@ def test_row_dealt_group_partitions_rows():
     finally:
         sharding.DEAL_ROWS = False
     assert list(shP.dealt) == [(1, 0)] and all(len(shP.local[et]) for et in [(1, 0), (0, 0), (0, 1)])
+
+
+def test_bench_dump_outputs_is_whole_when_small_and_a_fixed_sample_when_large(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float32 (other dtypes as float64),
+    whole while the total fits the budget; past it, the arrays above an equal share are cut to
+    the same sorted sample of elements on every call, and the total stays within the budget.
+    --full is off by default."""
+    import bench
+
+    assert bench.parse([]).full is False and bench.parse([]).dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full is True
+    assert bench.DUMP_BUDGET <= 64 << 20
+    rng = np.random.default_rng(0)
+    arrays = {"a": rng.standard_normal((300, 7)).astype(np.float32), "rows": np.arange(9, dtype=np.int32),
+              "loss": np.array([0.5], dtype=np.float32)}
+    bench.dump_outputs(tmp_path / "whole", arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == (np.float32 if v.dtype == np.float32 else np.float64)
+        assert got.shape == v.shape and np.array_equal(got, v)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 3000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(tmp_path / d, arrays)
+    total = 0
+    for k, v in arrays.items():
+        s1, s2 = np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy")
+        assert np.array_equal(s1, s2)
+        total += s1.nbytes
+    assert total <= 3000
+    a = np.load(tmp_path / "s1" / "a.npy")
+    assert a.shape == (250,) and np.all(np.isin(a, arrays["a"]))  # 1000 B share of float32
+    assert np.array_equal(np.load(tmp_path / "s1" / "rows.npy"), arrays["rows"])  # under its share: whole

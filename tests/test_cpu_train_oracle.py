@@ -165,26 +165,21 @@ def test_dropout_masks_distribution():
 
 
 def test_apk_restatement_matches_reference():
-    """oracle.apk against the reference's own rank_metrics.apk (decagon/utility/rank_metrics.py,
-    numpy-only, imported from /root/reference when present — this container)."""
-    import importlib.util
-    import os
+    """oracle.apk against the reference's own rank_metrics.apk (decagon/utility/rank_metrics.py):
+    the values it returned for these seeded rankings are stored, with the scores they rank, in
+    tests/golden/apk_reference.npz (tests/golden/make_golden.py apk)."""
+    from conftest import GOLDEN
 
-    path = "/root/reference/decagon/utility/rank_metrics.py"
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present (GPU box)")
-    os.environ.setdefault("PYTHONDONTWRITEBYTECODE", "1")
-    spec = importlib.util.spec_from_file_location("ref_rank_metrics", path)
-    mod = importlib.util.module_from_spec(spec)
-    import sys
-    sys.dont_write_bytecode = True
-    spec.loader.exec_module(mod)
+    z = np.load(GOLDEN / "apk_reference.npz", allow_pickle=False)
+    cases = ((100, 50), (30, 50), (500, 10))
+    assert [tuple(c) for c in z["cases"].tolist()] == list(cases)
     rng = np.random.default_rng(4)
-    for n, k in ((100, 50), (30, 50), (500, 10)):
+    for c, (n, k) in enumerate(cases):
         scores = rng.integers(0, 15, n).astype(float)
+        assert np.array_equal(scores, z[f"scores_{c}"])  # the ranking the stored value belongs to
         actual = list(range(n // 3))
         predicted = [i for _, i in sorted(zip(scores.tolist(), range(n)), reverse=True, key=lambda t: t[0])]
-        assert orc.apk(actual, predicted, k) == mod.apk(actual, predicted, k)
+        assert orc.apk(actual, predicted, k) == float(z["expected"][c])
 
 
 @pytest.mark.parametrize("dropout", [False, True])
