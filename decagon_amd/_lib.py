@@ -23,9 +23,10 @@ DG_STAGED_MAX_CHUNKS = 128
 DG_EPI_L2NORM = 1
 DG_EPI_RELU = 2
 DG_EPI_CHUNK_RELU = 4
-ABI_VERSION = 38
+ABI_VERSION = 39
 DG_HINGE_WS_BYTES = 16 + 4 * 256  # decagon_hip.h
 DG_RANK_LOGIT, DG_RANK_SIGMOID64, DG_RANK_SIGMOID32 = 0, 1, 2  # decagon_hip.h
+DG_TOPK_MAX_K, DG_TOPK_UPPER, DG_TOPK_NO_DIAG = 1024, 1, 2  # decagon_hip.h
 DG_GROUP_SHARED_PATTERN = 1  # dg_rel_group.flags
 DG_GROUP_DROPOUT = 2
 DG_GROUP_DENSE_ROWS = 4  # dg_gcn_fused_f32 only: row r of the group's sum is x[r]
@@ -292,6 +293,13 @@ SIGNATURES = {
                                          c_int64, c_void_p]),
     "dg_rank_metrics_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64,
                                       c_void_p]),
+    "dg_decoder_topk_workspace": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "dg_decoder_topk_f32": (
+        c_int32,
+        [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+         c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_int64, c_void_p],
+    ),
     "dg_unigram_sample_slots": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, ctypes.c_uint64,
                                           c_void_p, c_void_p]),
     "dg_unigram_sample": (

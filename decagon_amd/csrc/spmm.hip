@@ -736,7 +736,7 @@ __global__ __launch_bounds__(1024) void spmm_lds_kernel(const LdsArgs a) {
 
 }  // namespace
 
-extern "C" int32_t dg_abi_version(void) { return 38; }
+extern "C" int32_t dg_abi_version(void) { return 39; }
 
 
 namespace {

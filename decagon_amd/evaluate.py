@@ -62,6 +62,101 @@ def rank_metrics(pos: torch.Tensor, neg: torch.Tensor, k: int = 50,
     return au, ap, apk
 
 
+def _stacked_latents(ctx: RunContext, dec, d: int):
+    """(G, l) of ALL relations of one decoder for kernels.decoder_topk, as views of its flat
+    parameter buffer: DEDICOM the shared R [d, d] and local_variation_k at stride d ([K, d]);
+    Bilinear relation_k at stride d·d ([K, d, d]); DistMult's diagonals and InnerProduct's
+    identity expanded once per run to dense G, as runtime.latent_operands does."""
+    K = dec.num_types
+    specs = [dec.latent(k) for k in range(K)]
+    gk, _, lk, _ = specs[0]
+
+    def stack(vars_, per):  # K equally spaced variables of `per` floats → one [K, per] view
+        off0 = (vars_[0].tensor.data_ptr() - dec.flat.data_ptr()) // 4
+        for k, v in enumerate(vars_):
+            if (v.tensor.data_ptr() - dec.flat.data_ptr()) // 4 != off0 + k * per or v.tensor.numel() != per:
+                raise RuntimeError("decoder variables are not equally spaced in the flat buffer")
+        return dec.flat[off0:off0 + K * per].view(K, per)
+
+    if gk == "dense":
+        gvars = [s[1] for s in specs]
+        if all(v is gvars[0] for v in gvars):
+            G = gvars[0].tensor.contiguous()
+        else:
+            G = stack(gvars, d * d).view(K, d, d)
+    else:
+        key = ("topk_G", gk, id(dec), d)
+        if key not in ctx.cache:
+            ctx.cache[key] = (torch.eye(d, device=ctx.session.device) if gk == "eye"
+                              else torch.diag_embed(stack([s[1] for s in specs], d)).contiguous())
+        G = ctx.cache[key]
+    l = stack([s[3] for s in specs], d) if lk == "diag" else None
+    return G, l
+
+
+def _sigmoid_host(x: np.ndarray, mode: Optional[str]) -> np.ndarray:
+    """The reference's score of a float32 logit array (module docstring), on the host."""
+    if mode is None:
+        return x
+    with np.errstate(over="ignore"):
+        e = np.exp(-x.astype(np.float32))  # float32 exp, as both reference forms
+        if mode == "main":
+            return np.nan_to_num(1.0 / (1.0 + e.astype(np.float64)))
+        return (np.float32(1.0) / (np.float32(1.0) + e)).astype(np.float32)
+
+
+def top_candidates(sess, opt, placeholders, feed_dict, edge_type_ij, k: int, exclude=None, upper: bool = False,
+                   no_diag: bool = False, sigmoid: Optional[str] = None):
+    """For every relation of edge type (i, j), the k highest-scoring permitted pairs: numpy
+    (scores [K, k], rows [K, k], cols [K, k], counts [K]); slots past counts[r] hold −inf / −1.
+
+    What GreedyActiveLearner (main/ActiveLearner/GreedyActiveLearner.py:66-96) gets from
+    session.run(predictions) → sigmoid → np.take(candidates) → argsort()[::-1][:n], one relation
+    per run, here in one fused launch over all relations (dg_decoder_topk_f32): the model runs
+    forward at dropout 0 and no N_i×N_j matrix is formed.  `exclude`: None, a
+    sparse.ExclusionCSR, or one entry per relation as sparse.exclusion_csr takes them (e.g. the
+    training adjacencies); `upper` keeps r < c, `no_diag` drops r == c.
+
+    The ranking is by LOGIT (ties by smaller r·N_j + c).  `sigmoid` (a key of SIGMOID_MODES)
+    only transforms the returned scores.  The sigmoid is monotonic, so this is the reference's
+    ranking except inside saturated ties (logits the sigmoid maps to the same float, e.g. all
+    above ≈36.7 under "main"), where the reference's own order is whatever numpy's unstable
+    argsort leaves — unspecified."""
+    if sigmoid not in SIGMOID_MODES:
+        raise ValueError(f"sigmoid must be one of {list(SIGMOID_MODES)}")
+    i, j = edge_type_ij
+    model = opt._model()
+    if (i, j) not in model.edge_type2decoder:
+        raise ValueError(f"unknown edge type {(i, j)}")
+    dec = model.edge_type2decoder[i, j]
+    fd = dict(feed_dict)
+    fd[placeholders["dropout"]] = 0.0
+
+    def fn(ctx: RunContext):
+        ets = list(model.edge_types)
+        first = sum(model.edge_types[et] for et in ets[:ets.index((i, j))])  # flat index of relation 0
+        for r in range(first, first + dec.num_types):
+            if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
+                raise ValueError("top_candidates reads the decoder's variables; a latent matrix is fed")
+        row_t, col_t = opt._tables(ctx, i, j)
+        G, l = _stacked_latents(ctx, dec, row_t.shape[1])
+        if G.dim() == 2 and l is None and dec.num_types > 1:  # no per-relation parameter
+            G = G.unsqueeze(0).expand(dec.num_types, -1, -1).contiguous()
+        ex = exclude
+        if ex is not None and not hasattr(ex, "rowptr"):
+            from .sparse import exclusion_csr
+            ex = exclusion_csr(ex, (row_t.shape[0], col_t.shape[0]))
+        return kernels.decoder_topk(row_t, col_t, G, l, k, exclude=ex, upper=upper, no_diag=no_diag)
+
+    s, r, c, n = (np.asarray(t) for t in sess.run(Node("evaluate/top_candidates", fn), feed_dict=fd))
+    if sigmoid is not None:
+        valid = np.arange(s.shape[1])[None, :] < n[:, None]
+        out = np.full(s.shape, -np.inf, np.float64 if sigmoid == "main" else np.float32)
+        out[valid] = _sigmoid_host(s[valid], sigmoid)
+        s = out
+    return s, r, c, n
+
+
 def _pairs(edges) -> Tuple[np.ndarray, np.ndarray]:
     e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
     return e[:, 0].astype(np.int32), e[:, 1].astype(np.int32)

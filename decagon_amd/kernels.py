@@ -1272,6 +1272,94 @@ def decoder_score(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: tor
     return out
 
 
+def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor],
+                 topk: int, exclude=None, upper: bool = False, no_diag: bool = False, stream=None
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(scores [K, topk] float32, rows [K, topk] int32, cols [K, topk] int32, counts [K] int32):
+    per relation k the topk highest permitted pairs of (row_table[r] ∘ l_k)ᵀ·G_k·(l_k ∘ col_table[c])
+    (dg_decoder_topk_f32: higher score first, ties by smaller r·N_j + c, −0 as +0; slots past
+    counts[k] hold −inf / −1).  No N_i×N_j matrix is formed.
+
+    G: [d, d] (shared by every relation) or [K, d, d]; l: None (identity), [d] (shared) or [K, d].
+    K is the leading dimension of whichever is per relation (1 if neither), and of `exclude`.
+    exclude: None, a sparse.ExclusionCSR (uploaded here), or a (rowptr, col) pair of device int32
+    tensors in that layout (columns ascending and unique within each row).
+    upper: only r < c (square tables); no_diag: drop r == c."""
+    tabs = [(row_table, "row_table"), (col_table, "col_table"), (G, "G")] + ([(l, "l")] if l is not None else [])
+    for t, nm in tabs:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{nm}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{nm}: dtype {t.dtype}, expected {torch.float32}")
+        if not t.is_contiguous():
+            raise ValueError(f"{nm}: must be contiguous")
+    if row_table.dim() != 2 or col_table.dim() != 2 or G.dim() not in (2, 3):
+        raise ValueError("decoder_topk: tables must be [N, d] and G [d, d] or [K, d, d]")
+    d = G.shape[-1]
+    if G.shape[-2] != d or row_table.shape[1] != d or col_table.shape[1] != d:
+        raise ValueError("decoder_topk: d mismatch")
+    if l is not None and (l.dim() not in (1, 2) or l.shape[-1] != d):
+        raise ValueError("decoder_topk: d mismatch (l must be [d] or [K, d])")
+    if d not in (32, 64):
+        raise ValueError(f"decoder_topk: d = {d} unsupported (32 or 64)")
+    topk = int(topk)
+    if not 1 <= topk <= _lib.DG_TOPK_MAX_K:
+        raise ValueError(f"decoder_topk: topk must be in [1, {_lib.DG_TOPK_MAX_K}]")
+    n_rows, n_cols = row_table.shape[0], col_table.shape[0]
+    if n_rows < 1 or n_cols < 1 or n_rows * n_cols >= 2**32:
+        raise ValueError("decoder_topk: needs 1 <= N_i·N_j < 2^32")
+    if upper and n_rows != n_cols:
+        raise ValueError("decoder_topk: upper needs square tables")
+    ks = {int(t.shape[0]) for t, per in ((G, G.dim() == 3), (l, l is not None and l.dim() == 2)) if per}
+    ex_rowptr = ex_col = None
+    if exclude is not None:
+        if hasattr(exclude, "rowptr") and hasattr(exclude, "n_rels"):
+            if (exclude.n_rows, exclude.n_cols) != (n_rows, n_cols):
+                raise ValueError("decoder_topk: exclusion shape does not match the tables")
+            ks.add(int(exclude.n_rels))
+            ex_rowptr, ex_col = exclude.rowptr, exclude.col
+        else:
+            ex_rowptr, ex_col = exclude
+            if (ex_rowptr.numel() - 1) % n_rows:
+                raise ValueError("decoder_topk: exclusion rowptr must have K·N_i + 1 entries")
+            ks.add((ex_rowptr.numel() - 1) // n_rows)
+    if len(ks) > 1:
+        raise ValueError(f"decoder_topk: relation counts disagree: {sorted(ks)}")
+    K = ks.pop() if ks else 1
+    if K < 1:
+        raise ValueError("decoder_topk: no relations")
+    for t, nm in tabs:
+        if not t.is_cuda:
+            raise ValueError(f"{nm}: must be a device (HIP) tensor")
+    dev = G.device
+    if isinstance(ex_rowptr, np.ndarray):
+        ex_rowptr, ex_col = torch.from_numpy(ex_rowptr).to(dev), torch.from_numpy(ex_col).to(dev)
+    if ex_rowptr is not None:
+        _dev(ex_rowptr, torch.int32, "exclude rowptr")
+        _dev(ex_col, torch.int32, "exclude col")
+        if ex_rowptr.numel() != K * n_rows + 1:
+            raise ValueError("decoder_topk: exclusion rowptr must have K·N_i + 1 entries")
+        if ex_col.numel() == 0:
+            ex_rowptr = ex_col = None  # nothing excluded
+    lib = _lib.load()
+    nbytes = int(lib.dg_decoder_topk_workspace(K, n_rows, n_cols, topk))
+    ws = torch.empty(-(-nbytes // 8), dtype=torch.int64, device=dev)
+    scores = torch.empty((K, topk), dtype=torch.float32, device=dev)
+    rows = torch.empty((K, topk), dtype=torch.int32, device=dev)
+    cols = torch.empty((K, topk), dtype=torch.int32, device=dev)
+    counts = torch.empty(K, dtype=torch.int32, device=dev)
+    flags = (_lib.DG_TOPK_UPPER if upper else 0) | (_lib.DG_TOPK_NO_DIAG if no_diag else 0)
+    check(lib.dg_decoder_topk_f32(
+        row_table.data_ptr(), d, n_rows, col_table.data_ptr(), d, n_cols, G.data_ptr(),
+        d * d if G.dim() == 3 else 0, l.data_ptr() if l is not None else None,
+        d if (l is not None and l.dim() == 2) else 0, K, d, topk,
+        ex_rowptr.data_ptr() if ex_rowptr is not None else None,
+        ex_col.data_ptr() if ex_col is not None else None, flags, scores.data_ptr(), rows.data_ptr(),
+        cols.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream_ptr(stream)),
+        "dg_decoder_topk_f32")
+    return scores, rows, cols, counts
+
+
 def decoder_score_bf16(row_table: torch.Tensor, col_table: torch.Tensor, rows: torch.Tensor,
                        cols: torch.Tensor, G: torch.Tensor, l_table: Optional[torch.Tensor] = None,
                        rel: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,

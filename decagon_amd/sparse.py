@@ -169,6 +169,60 @@ def stack_relations(csrs: Sequence[HostCSR]) -> StackedCSR:
 
 
 @dataclass
+class ExclusionCSR:
+    """Per-relation exclusion sets of dg_decoder_topk_f32, stacked like StackedCSR (no values):
+    relation k's row r excludes col[rowptr[k*n_rows + r] : rowptr[k*n_rows + r + 1]], ascending
+    and unique — the order the kernel's ABI requires."""
+
+    rowptr: np.ndarray
+    col: np.ndarray
+    n_rows: int
+    n_cols: int
+    n_rels: int
+
+    @property
+    def nnz(self) -> int:
+        return int(self.col.shape[0])
+
+
+def exclusion_csr(mats_or_coo_list, shape) -> ExclusionCSR:
+    """Stack one exclusion set per relation for kernels.decoder_topk.  Each entry is a scipy
+    sparse matrix (its stored pattern, whatever the values), a COO tuple (coords, values, shape),
+    an [nnz, 2] array of (row, col) pairs, or None (nothing excluded).  Unlike coo_to_csr, which
+    keeps feed order inside a row, the columns of every row are sorted and de-duplicated."""
+    n_r, n_c = int(shape[0]), int(shape[1])
+    if n_r < 1 or n_c < 1 or n_r >= 2**31 or n_c >= 2**31:
+        raise ValueError(f"bad exclusion shape {shape}")
+    entries = list(mats_or_coo_list)
+    if not entries:
+        raise ValueError("empty relation list")
+    rowptr = np.zeros(len(entries) * n_r + 1, np.int64)
+    cols = []
+    for k, e in enumerate(entries):
+        if e is None:
+            coords = np.zeros((0, 2), np.int64)
+        elif sp.issparse(e) or (isinstance(e, (tuple, list)) and len(e) == 3 and np.ndim(e[0]) == 2):
+            coords, _, shp = as_coo_tuple(e)
+            if tuple(int(x) for x in shp) != (n_r, n_c):
+                raise ValueError(f"relation {k}: shape {tuple(shp)} != {(n_r, n_c)}")
+        else:
+            coords = np.asarray(e)
+        coords = np.asarray(coords).astype(np.int64).reshape(-1, 2) if np.size(coords) else np.zeros((0, 2), np.int64)
+        r, c = coords[:, 0], coords[:, 1]
+        if r.size and (r.min() < 0 or r.max() >= n_r or c.min() < 0 or c.max() >= n_c):
+            raise ValueError(f"relation {k}: exclusion index out of range for shape {(n_r, n_c)}")
+        lin = np.unique(r * n_c + c)  # sorted by (row, col), duplicates dropped
+        rowptr[k * n_r + 1:(k + 1) * n_r + 1] = np.cumsum(np.bincount(lin // n_c, minlength=n_r))
+        cols.append((lin % n_c).astype(np.int32))
+    for k in range(1, len(entries)):  # per-relation cumulative counts → global offsets
+        rowptr[k * n_r + 1:(k + 1) * n_r + 1] += rowptr[k * n_r]
+    if rowptr[-1] >= 2**31:
+        raise ValueError("exclusion sets exceed int32 offsets")
+    col = np.concatenate(cols) if cols else np.zeros(0, np.int32)
+    return ExclusionCSR(rowptr.astype(np.int32), col.astype(np.int32), n_r, n_c, len(entries))
+
+
+@dataclass
 class MergedCSR:
     """A group's relations in the chunk-merged layout of dg_rel_group (decagon_hip.h):
     for chunk c and row r the nonzeros of every relation of the chunk, contiguous, at

@@ -36,7 +36,8 @@ extern "C" {
 
 #define DG_MAX_GROUPS 8
 
-/* ABI version (36); bumped whenever a struct layout or a signature changes (36: DG_PEER_STATE_WORDS grew). */
+/* ABI version (39); bumped whenever a struct layout or a signature changes or an entry point is added
+ * (36: DG_PEER_STATE_WORDS grew; 39: dg_decoder_topk_f32). */
 int32_t dg_abi_version(void);
 
 /* --------------------------------------------------------------------------------------
@@ -809,6 +810,53 @@ int dg_rank_metrics_f32(const float* pos, int32_t n_pos, const float* neg, int32
 int64_t dg_rank_metrics_ex_workspace(int32_t n_pos, int32_t n_neg);
 int dg_rank_metrics_ex_f32(const float* pos, int32_t n_pos, const float* neg, int32_t n_neg, int32_t k,
                            int32_t mode, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * Top-k candidate ranking (ABI 39): for every relation k < n_rel of one edge type, the `topk`
+ * highest-scoring permitted pairs (r, c), r < n_rows, c < n_cols, of
+ *
+ *     s_k[r, c] = (row_table[r] ∘ l_k)ᵀ · G_k · (l_k ∘ col_table[c])          (fp32, MFMA)
+ *
+ * without forming any n_rows x n_cols matrix.
+ * Replaces: session.run(predictionsTensor) → sigmoid → np.take(candidates) → argsort()[::-1][:n]
+ *           main/ActiveLearner/GreedyActiveLearner.py:66-96; the E·D·R·D·Eᵀ matrix of
+ *           main/Predictor/NpPredictor.py:293-313.
+ *
+ * Operands: row_table / col_table: row r at table + r*ld (ld >= d, ld % 4 == 0, 16-byte aligned);
+ * G_k = G + k*g_stride, g_stride 0 (one shared d x d G: DEDICOM's R) or d*d (per relation:
+ * Bilinear), row-major; l_k = l + k*l_stride, l_stride 0 (shared) or d (per relation), l NULL =
+ * identity.  d is 32 or 64; 1 <= topk <= DG_TOPK_MAX_K; n_rows * n_cols < 2^32.
+ *
+ * Permitted: (r, c) is not in relation k's exclusion set; with DG_TOPK_UPPER only r < c (needs
+ * n_rows == n_cols); with DG_TOPK_NO_DIAG not r == c.  The exclusion sets are a relation-stacked
+ * CSR (as StackedCSR, without values): relation k's row r excludes the columns
+ * excl_col[excl_rowptr[k*n_rows + r] .. excl_rowptr[k*n_rows + r + 1]), which MUST be ascending
+ * and unique within the row (the kernel walks them once beside its column tiles; unsorted
+ * columns give a wrong selection, never an out-of-range access).  Rows may be empty, a relation
+ * may exclude everything; excl_rowptr == excl_col == NULL excludes nothing (one of them NULL
+ * alone is an error).
+ *
+ * Ordering (total, so the result is unique and independent of tiling, grid and scheduling):
+ * higher fp32 score first; equal scores by smaller linear index r*n_cols + c first; −0 compares
+ * (and is returned) as +0.  Non-finite scores are ordered by their bit pattern (sign-magnitude
+ * order of the float's bits: +NaN above +inf, −NaN below −inf) with no further promise.
+ *
+ * Outputs: out_score float [n_rel x topk], out_row / out_col int32 [n_rel x topk], descending in
+ * that ordering; out_count int32 [n_rel] = min(topk, permitted pairs); slots past out_count[k]
+ * hold −inf and −1.  Workspace: dg_decoder_topk_workspace(n_rel, n_rows, n_cols, topk) bytes
+ * (0 for arguments out of range), 16-byte aligned: topk 8-byte keys per 32 rows and relation —
+ * it grows with n_rows, never with n_rows * n_cols.
+ * -------------------------------------------------------------------------------------- */
+#define DG_TOPK_MAX_K 1024
+#define DG_TOPK_UPPER 1
+#define DG_TOPK_NO_DIAG 2
+int64_t dg_decoder_topk_workspace(int32_t n_rel, int32_t n_rows, int32_t n_cols, int32_t topk);
+int dg_decoder_topk_f32(const float* row_table, int64_t ld_row, int32_t n_rows, const float* col_table,
+                        int64_t ld_col, int32_t n_cols, const float* G, int64_t g_stride, const float* l,
+                        int64_t l_stride, int32_t n_rel, int32_t d, int32_t topk,
+                        const int32_t* excl_rowptr, const int32_t* excl_col, int32_t flags,
+                        float* out_score, int32_t* out_row, int32_t* out_col, int32_t* out_count,
+                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * Unigram negative sampler (T11):  out[i] ~ Categorical(p), p_c ∝ degree_c^0.75, draw
