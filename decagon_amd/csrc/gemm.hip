@@ -509,7 +509,8 @@ extern "C" int dg_gemm_tn_f32(const float* a, int64_t lda, int64_t a_bs, const f
     if (M < 32 || N < 32 || (M & 31) || (N & 31) || (M / 32) * (N / 32) > 4) return DG_EINVAL;
     if (lda < M || ldb < N) return DG_EINVAL;
     if (batch == 0) return DG_OK;
-    if (!a || !b || !c || (n_split > 1 && !partial)) return DG_EINVAL;
+    // (rows == 0: no row of a or b is read, and an empty device buffer's pointer may be null)
+    if ((rows > 0 && (!a || !b)) || !c || (n_split > 1 && !partial)) return DG_EINVAL;
     if (n_split > 1 && !dg::aligned16(partial)) return DG_EALIGN;
     TnArgs t{a, b, n_split > 1 ? partial : c, lda, a_bs, ldb, b_bs, rows, M, N, batch, n_split,
              2 * dg::ceil_div(dg::ceil_div(rows, n_split), 2)};

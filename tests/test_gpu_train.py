@@ -245,6 +245,7 @@ def test_adam_kernel_matches_tf_restatement():
     for i in range(len(sizes)):
         assert np.max(np.abs(dp[i].cpu().numpy() - p[i])) <= 1e-6
         assert np.max(np.abs(st.m[i].cpu().numpy() - m[i])) <= 1e-6
+        assert np.max(np.abs(st.v[i].cpu().numpy() - v[i])) <= 1e-6
     assert abs(float(st.state[2]) - train.adam_alpha(0.01, 4)) <= 1e-7
 
 
