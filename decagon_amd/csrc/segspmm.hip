@@ -352,8 +352,9 @@ constexpr int kFsMaxRpb = 4;  // rows per workgroup, at most (1: no change at co
 constexpr int kFsProfSlots = 8;
 constexpr int kFsProfMaxBlocks = 4096;
 __device__ unsigned long long g_fs_prof[2][kFsProfMaxBlocks][16][kFsProfSlots];
+// (kFsForm, a constant of the stamping function: 0 = the layer-1 launch, 1 = the layer-2 launch)
 #define DG_FS_STAMP(i) \
-    do { if (lane == 0 && blockIdx.x < kFsProfMaxBlocks) g_fs_prof[PROJ][blockIdx.x][wave][i] = __builtin_amdgcn_s_memrealtime(); } while (0)
+    do { if (lane == 0 && blockIdx.x < kFsProfMaxBlocks) g_fs_prof[kFsForm][blockIdx.x][wave][i] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define DG_FS_STAMP(i) ((void)0)
 #endif
@@ -364,6 +365,7 @@ __global__ __launch_bounds__(64 * NW) void gcn_fused_seg_kernel(const FsArgs a) 
     __shared__ float4 ybuf[NW][16];
     __shared__ float4 zbuf[NW][DOUT4];
     __shared__ float4 nbuf[kFsMaxRpb][DG_MAX_GROUPS][DOUT4];
+    [[maybe_unused]] constexpr int kFsForm = PROJ ? 1 : 0;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     DG_FS_STAMP(0);  // (profiling build: wave start)
@@ -453,7 +455,7 @@ __global__ __launch_bounds__(64 * NW) void gcn_fused_seg_kernel(const FsArgs a) 
     if (lane == 0 && blockIdx.x < kFsProfMaxBlocks) {
         uint32_t xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_fs_prof[PROJ][blockIdx.x][wave][7] = xcc;
+        g_fs_prof[kFsForm][blockIdx.x][wave][7] = xcc;
     }
 #endif
     if constexpr (PEER) dg::peer_arrive(a.P);  // the last workgroup raises the flags and waits
@@ -477,12 +479,15 @@ static_assert(sizeof(dg_tab_desc) == 64, "dg_tab_desc: one s_load_dwordx16");
 // of 64 pairs, the first from the slot, the rest from ovf, each prefetched before the batch
 // before it is gathered; U gathers in flight per lane, the pairs handed out by DPP row
 // broadcasts (seg_gather's: pair m·G + sub of a batch in lane 16·sub + m).  PROJ: then the
-// 64-wide aggregate times the relation's W slab (seg_wave_proj's arithmetic).
-template <bool PROJ, int U>
+// 64-wide aggregate times the relation's W slab (seg_wave_proj's arithmetic).  LP = 8 (32-float
+// rows, plain sums only): eight pairs handed out at once, pair 8m + sub of a batch in lane
+// 8·sub + m — seg_gather<8>'s order, so a lane group adds the same pairs in the same order.
+template <bool PROJ, int U, int LP = 16>
 __device__ __forceinline__ float4 tab_wave(const dg_tab_desc& D, const uint2 first, const uint2* __restrict__ ovf,
                                            float4* ybuf, const int S) {
-    constexpr int LP = 16;
+    static_assert(LP == 16 || (LP == 8 && !PROJ), "tab_wave: 64-float rows, or 32-float plain sums");
     constexpr int G = dg::kWave / LP;
+    [[maybe_unused]] constexpr int kFsForm = 1;  // (profiling build: only the reassociated form stamps here)
     const int lane = threadIdx.x & 63;
     float4 res = make_float4(0.f, 0.f, 0.f, 0.f);
     if (D.cnt > 0) {  // wave-uniform
@@ -517,6 +522,7 @@ __device__ __forceinline__ float4 tab_wave(const dg_tab_desc& D, const uint2 fir
             // measured 5.64–5.72 → 5.33–5.48 µs against the ds_bpermute hand-out (same pair order
             // per lane group: the same bits).
             constexpr int S = dg::kWave / G;
+            static_assert(U >= 1 && U <= S && S % U == 0, "tab_wave: the unroll must divide the steps of a batch");
 #pragma unroll
             for (int it = 0; it < S / U; ++it) {
                 if (it * U * G >= n) break;  // wave-uniform
@@ -524,8 +530,17 @@ __device__ __forceinline__ float4 tab_wave(const dg_tab_desc& D, const uint2 fir
                 float w[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    o[u] = row_bcast_rt(eoff, it * U + u);
-                    w[u] = __int_as_float(row_bcast_rt(vbits, it * U + u));
+                    const int m = it * U + u;
+                    if constexpr (LP == 16) {
+                        o[u] = row_bcast_rt(eoff, m);
+                        w[u] = __int_as_float(row_bcast_rt(vbits, m));
+                    } else {  // a 16-lane row holds two lane groups' pairs: lanes 0-7 and 8-15
+                        const bool odd = (lane >> 3) & 1;
+                        const int o0 = row_bcast_rt(eoff, m), o1 = row_bcast_rt(eoff, 8 + m);
+                        const int w0 = row_bcast_rt(vbits, m), w1 = row_bcast_rt(vbits, 8 + m);
+                        o[u] = odd ? o1 : o0;
+                        w[u] = __int_as_float(odd ? w1 : w0);
+                    }
                 }
                 float4 xv[U];
 #pragma unroll
@@ -615,23 +630,55 @@ __device__ __forceinline__ float4 lds_ordered_sum(const float4 (*rows)[W], int K
 
 // Byte offset of this lane's first-batch pair in a slot of S pairs: lane 16·sub + m' holds pair
 // 4m' + sub, stored at slot entry sub·S/4 + m'; lanes with m' >= S/4 (no such pair in the slot)
-// read their row's last entry — the same cache lines, never used.
+// read their row's last entry — the same cache lines, never used.  LP = 8: lane 8·sub + m' holds
+// pair 8m' + sub, stored at slot entry sub·S/8 + m'.
+template <int LP = 16>
 __device__ __forceinline__ uint32_t slot_lane_offset(int lane, int S) {
-    const int q = S >> 2, m = lane & 15;
-    return 8u * (uint32_t)((lane >> 4) * q + (m < q ? m : q - 1));
+    constexpr int G = dg::kWave / LP;
+    const int q = S / G, m = lane & (LP - 1);
+    return 8u * (uint32_t)((lane / LP) * q + (m < q ? m : q - 1));
+}
+
+// A float4 read as a global_load (the pointer is known to address device memory), not the flat
+// load a pointer out of a descriptor gets.
+__device__ __forceinline__ float4 load4_global(const float* p) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    const v4f v = *(const v4f __attribute__((address_space(1)))*)(uintptr_t)p;
+    return make_float4(v.x, v.y, v.z, v.w);
 }
 
 // PEER (dg_gcn_fused_tab_peer_f32): each finished row also goes to every peer's copy of its
 // target (desc.pad[0] = the row's byte offset in the target, pad[1] = the target's bytes), and
 // the launch ends with the exchange (peer.h).
-template <bool PROJ, int NW, bool PEER>
+// LP = 8: the 32 -> 32 instance (plain sums over a 32-float operand, gcn_fused_seg_kernel<8, false>'s
+// rows bit for bit when every wave holds one relation).
+// POST (dg_gcn_fused_tab_post_f32; layer 1, 64 -> 64): the layer-2 operands P_k = H1·W2_k of the
+// workgroup's rows are made here, where the H1 rows are born.  The finishing wave also leaves its
+// row in LDS, one more barrier follows, and every wave whose descriptor carries a projection job
+// (role bit 30; its row slots in the mask of bits 24-27, W2_k in desc.w, the P row of row slot 0
+// in pad[0..1], slot s's row 128 bytes · s further) multiplies each of those rows by its W slab —
+// tab_wave<PROJ>'s lane mapping and arithmetic — and stores the 32 floats: one slice load serves
+// every row of the workgroup that the relation is sourced from.
+// A wave's eight W-slice loads are issued once its own gathers are done, before the first
+// barrier, so their round trip passes while the wave waits there and while the finishing wave
+// works: the slice is not live across the gather loop (74-76 VGPRs and slower, round 4), and no
+// load trails the row as in round 2's serial projection epilogue.  (Measured at config S, layer
+// 1 alone: 4.25 us without jobs, 5.46 with one (row, relation) a wave, 5.31 with a wave taking
+// both gene rows of its workgroup, 5.26 with the loads issued after the first barrier instead —
+// no difference — and 4.87 with the slice not loaded at all: the second barrier, the FMAs and
+// the P store cost 0.6 us, the slabs' L2 -> CU traffic 0.45.)
+template <bool PROJ, int NW, bool PEER, int LP = 16, bool POST = false>
 __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restrict__ pairs,
                                                           const dg_tab_desc* __restrict__ desc,
                                                           const uint2* __restrict__ ovf, const int S,
                                                           const dg::PeerK P) {
-    constexpr int DOUT4 = PROJ ? 8 : 16;
+    static_assert(LP == 16 || (LP == 8 && !PROJ && !PEER), "gcn_tab_kernel: 32-float rows in the plain one-GPU form");
+    static_assert(!POST || (LP == 16 && !PROJ && !PEER), "gcn_tab_kernel: the projecting tail follows a 64 -> 64 layer");
+    constexpr int DOUT4 = PROJ ? 8 : LP;
+    [[maybe_unused]] constexpr int kFsForm = (PROJ || LP == 8) ? 1 : 0;
     __shared__ float4 ybuf[NW][16];
     __shared__ float4 zbuf[NW][DOUT4];
+    __shared__ float4 hbuf[POST ? kFsMaxRpb : 1][16];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t wi = (int64_t)blockIdx.x * NW + wave;
@@ -644,17 +691,32 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
     const dg_tab_desc D = desc[wi];  // (uniform: scalar loads)
     uint2 first;
     asm volatile("global_load_dwordx2 %0, %1, %2\n\ts_waitcnt vmcnt(0)"
-                 : "=&v"(first) : "v"(slot_lane_offset(lane, S)), "s"(pairs + wi * S) : "memory");
+                 : "=&v"(first) : "v"(slot_lane_offset<LP>(lane, S)), "s"(pairs + wi * S) : "memory");
     // every descriptor field and the ovf base in SGPRs here, so no scalar load is sunk below
     // the branch into a round trip of its own
     asm volatile("" ::"s"(D.x), "s"(D.w), "s"(D.orow), "s"(D.cnt), "s"(D.x_ld), "s"(D.ovf), "s"(D.role), "s"(D.wr),
                  "s"(ovf));
+    if constexpr (POST) asm volatile("" ::"s"(D.pad[0]), "s"(D.pad[1]));
 #ifdef DG_FSEG_PROF
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #endif
     DG_FS_STAMP(1);  // descriptor and first pairs in registers
     if constexpr (!PROJ) DG_FS_STAMP(2);  // (layer 2: stamp 2 marks its gathers done, in tab_wave)
-    const float4 res = tab_wave<PROJ, PROJ ? kTabUP : kTabU>(D, first, ovf, ybuf[wave], S);
+    const float4 res = tab_wave<PROJ, PROJ ? kTabUP : kTabU, LP>(D, first, ovf, ybuf[wave], S);
+    // POST: this lane's slice of the job's W2_k (rows 8(l>>3) .. +8, output float4 l & 7), issued
+    // now that the gathers are folded (res) and waited for only after the second barrier
+    const bool pjob = POST && ((D.role >> 30) & 1u);  // wave-uniform
+    const int ms = lane >> 3;
+    float4 wv[POST ? 8 : 1];  // (read only under pjob)
+    if constexpr (POST) {
+        if (pjob) {
+            // global-address-space loads: a flat load would also count as an LDS operation, and
+            // the wait for zbuf's write before the barrier would then wait for the slice too
+            const float* w = D.w + 4 * ((8 * ms) * 8 + (lane & 7));
+#pragma unroll
+            for (int i = 0; i < 8; ++i) wv[i] = load4_global(w + 4 * 8 * i);
+        }
+    }
 #ifdef DG_FSEG_PROF
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #endif
@@ -696,18 +758,45 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
                 tot.w = fmaxf(tot.w, 0.f);
             }
             reinterpret_cast<float4*>(D.orow)[lane] = tot;
+            if constexpr (POST) hbuf[(D.wr >> 16) & (kFsMaxRpb - 1)][lane] = tot;  // the row as stored
             if constexpr (PEER)
                 dg::peer_store4(P, reinterpret_cast<const float*>(reinterpret_cast<const char*>(D.orow) - D.pad[0]),
                                 (uint32_t)D.pad[1], (uint32_t)D.pad[0] + 16u * lane, tot);
         }
     }
+    if constexpr (POST) {
+        __syncthreads();  // the workgroup's H1 rows in hbuf
+        if (pjob) {
+            // z = h·W2_k, tab_wave<PROJ>'s arithmetic: 32 fmaf over this lane's 8-row slice, then
+            // the butterfly over the 8 slices; lanes 0-7 hold the 32 floats of the P row
+            float4* prow = reinterpret_cast<float4*>(((uint64_t)(uint32_t)D.pad[1] << 32) | (uint32_t)D.pad[0]);
+            const uint32_t slots = (D.role >> 24) & ((1u << kFsMaxRpb) - 1u);
+#pragma unroll
+            for (int sl = 0; sl < kFsMaxRpb; ++sl) {
+                if (!((slots >> sl) & 1u)) continue;  // wave-uniform
+                const float4 ya = hbuf[sl][2 * ms];
+                const float4 yb = hbuf[sl][2 * ms + 1];
+                float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+                dg::fma4(z, ya.x, wv[0]);
+                dg::fma4(z, ya.y, wv[1]);
+                dg::fma4(z, ya.z, wv[2]);
+                dg::fma4(z, ya.w, wv[3]);
+                dg::fma4(z, yb.x, wv[4]);
+                dg::fma4(z, yb.y, wv[5]);
+                dg::fma4(z, yb.z, wv[6]);
+                dg::fma4(z, yb.w, wv[7]);
+                z = dg::xor_sum4_from<8>(z);
+                if (lane < 8) prow[8 * sl + lane] = z;
+            }
+        }
+    }
 #ifdef DG_FSEG_PROF
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    DG_FS_STAMP(6);  // row stored
+    DG_FS_STAMP(6);  // row stored (POST: and the wave's P row)
     if (lane == 0 && blockIdx.x < kFsProfMaxBlocks) {
         uint32_t xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_fs_prof[PROJ][blockIdx.x][wave][7] = xcc;
+        g_fs_prof[kFsForm][blockIdx.x][wave][7] = xcc;
     }
 #endif
     if constexpr (PEER) dg::peer_arrive(P);  // the last workgroup raises the flags and waits
@@ -945,10 +1034,14 @@ extern "C" int dg_gcn_fused_seg_f32(const dg_seg_group* groups, int32_t n_groups
 }
 
 namespace {
-int fused_tab_launch(const dg_wave_table* t, int32_t d_in, int32_t d_out, const dg_peer_xchg* xchg, void* stream) {
+int fused_tab_launch(const dg_wave_table* t, int32_t d_in, int32_t d_out, const dg_peer_xchg* xchg, bool post,
+                     void* stream) {
     if (!t) return DG_EINVAL;
     bool proj = false;
-    if (seg_shape(d_in, d_out, proj) != DG_OK || (!proj && d_in != 64)) return DG_EINVAL;
+    if (seg_shape(d_in, d_out, proj) != DG_OK) return DG_EINVAL;
+    const bool narrow = !proj && d_in == 32;  // the 32 -> 32 instance: one GPU, no exchange
+    if (narrow && xchg) return DG_EINVAL;
+    if (post && (xchg || proj || d_in != 64)) return DG_EINVAL;  // the projecting tail: after a 64 -> 64 layer
     if (t->n_blocks < 0 || t->nw < 1 || t->nw > 16 || t->nw_stride != (t->nw <= 8 ? 8 : 16)) return DG_EINVAL;
     if (t->n_blocks == 0) return xchg ? DG_EINVAL : DG_OK;  // (an exchange needs a workgroup a rank)
     if (!t->pairs || !t->desc || !dg::aligned16(t->pairs) || (reinterpret_cast<uintptr_t>(t->desc) & 63))
@@ -965,9 +1058,13 @@ int fused_tab_launch(const dg_wave_table* t, int32_t d_in, int32_t d_out, const 
     const uint2* ov = reinterpret_cast<const uint2*>(t->ovf);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     dim3 grid(static_cast<unsigned>(t->n_blocks)), block(64 * t->nw);
-#define DG_TAB_LAUNCH(PR, NWV, PE) \
-    hipLaunchKernelGGL((gcn_tab_kernel<PR, NWV, PE>), grid, block, 0, st, pr, t->desc, ov, S, P)
-    if (xchg) {
+#define DG_TAB_LAUNCH(PR, NWV, PE, ...) \
+    hipLaunchKernelGGL((gcn_tab_kernel<PR, NWV, PE, ##__VA_ARGS__>), grid, block, 0, st, pr, t->desc, ov, S, P)
+    if (narrow) {
+        if (t->nw_stride == 8) DG_TAB_LAUNCH(false, 8, false, 8); else DG_TAB_LAUNCH(false, 16, false, 8);
+    } else if (post) {
+        if (t->nw_stride == 8) DG_TAB_LAUNCH(false, 8, false, 16, true); else DG_TAB_LAUNCH(false, 16, false, 16, true);
+    } else if (xchg) {
         if (t->nw_stride == 8) {
             if (proj) DG_TAB_LAUNCH(true, 8, true); else DG_TAB_LAUNCH(false, 8, true);
         } else {
@@ -986,13 +1083,17 @@ int fused_tab_launch(const dg_wave_table* t, int32_t d_in, int32_t d_out, const 
 }  // namespace
 
 extern "C" int dg_gcn_fused_tab_f32(const dg_wave_table* t, int32_t d_in, int32_t d_out, void* stream) {
-    return fused_tab_launch(t, d_in, d_out, nullptr, stream);
+    return fused_tab_launch(t, d_in, d_out, nullptr, false, stream);
+}
+
+extern "C" int dg_gcn_fused_tab_post_f32(const dg_wave_table* t, int32_t d_in, int32_t d_out, void* stream) {
+    return fused_tab_launch(t, d_in, d_out, nullptr, true, stream);
 }
 
 extern "C" int dg_gcn_fused_tab_peer_f32(const dg_wave_table* t, int32_t d_in, int32_t d_out,
                                          const dg_peer_xchg* xchg, void* stream) {
     if (!xchg) return DG_EINVAL;
-    return fused_tab_launch(t, d_in, d_out, xchg, stream);
+    return fused_tab_launch(t, d_in, d_out, xchg, false, stream);
 }
 
 extern "C" int dg_spmm_seg_tab_f32(const dg_wave_table* t, int32_t d_in, int32_t d_out, void* stream) {

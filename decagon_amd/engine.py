@@ -99,6 +99,17 @@ WAVE_TABLE = knob("DG_WAVE_TABLE", True)
 # (PreparedFusedTab balance, round 6) instead of one wave per relation: 0 never, 1 layer 1 only
 # (d_in == d_out), 2 both layers
 TAB_BALANCE = knob("DG_TAB_BALANCE", 1)
+# one-GPU forward plans in the wave-table fused form (config S): layer 1's workgroups also make
+# layer 2's operands P_k = H1_j·W2_k from the rows they finish (dg_gcn_fused_tab_post_f32: the
+# reference's own order, layers.py:113-114), and layer 2 is a plain 32-wide gather-sum over the P
+# stacks — half the gather bytes of the reassociated form, no W slab per (row, relation) wave, and
+# free to deal a row's pairs over every wave as layer 1 does.  DG_L2_PREPROJECT=0, training,
+# dropout, sharded plans, and plans whose projection jobs do not fit a workgroup's waves keep the
+# reassociated layer 2
+L2_PREPROJECT = knob("DG_L2_PREPROJECT", True)
+# ... one wave projecting every row of its workgroup onto a relation (the W slab read once a
+# workgroup: config S's layer 1 5.46 -> 5.31 us); 0: one (row, relation) a wave
+L2_PREPROJECT_SHARE = knob("DG_L2_PREPROJECT_SHARE", True)
 STAGED_FIRST = knob("DG_STAGED_FIRST", True)
 # sharded forward plans: layer 2 of the non-staged groups reassociated over the rank's own rows
 # and relations, Σ_k (Â_k·H1_j)·W2_k in dg_spmm_seg_f32, instead of every rank projecting all of
@@ -699,8 +710,12 @@ class ForwardPlan:
                                   and not g.staged for g in dgraph.groups.values())
                           and all(sum(dgraph.groups[et].n_rels for et in ets) <= 16
                                   for ets in self.targets.values()))
+        # ... or, L2_PREPROJECT, layer 2's operands made by layer 1's launch (self.proj), layer 2 a
+        # plain gather-sum over them
+        self.preproj = set(self.edge_types) if self._preproject_fits(keep_sums) else set()
         self.seg_proj = {et for et in self.edge_types
-                         if (self.seg_mode or self.fused_seg) and dgraph.groups[et].n_rels and h1 == 64 and h2 == 32}
+                         if (self.seg_mode or self.fused_seg) and dgraph.groups[et].n_rels and h1 == 64 and h2 == 32
+                         and et not in self.preproj}
         # sharded forward plans: every other non-staged group's layer 2 reassociated as well, over
         # the rank's own rows / relations (config P: PPI in its one-chunk layout, (0,1), (1,0)),
         # so no rank runs a projection GEMM over all of H1 (REASSOC_ROWS)
@@ -738,7 +753,7 @@ class ForwardPlan:
         finished = (set(self.targets) - set(self.row_block)) if self.flat_mode else set(self.fused)
         proj_fused = [et for et in self.edge_types
                       if dgraph.groups[et].n_rels and et[1] in finished and et not in self.staged_proj
-                      and et not in self.seg_proj
+                      and et not in self.seg_proj and et not in self.preproj
                       and rels_from[et[1]] <= self.FUSED_PROJ_MAX_RELS and self.drop_state is None]
         if len(proj_fused) > DG_MAX_GROUPS:
             proj_fused = []
@@ -748,14 +763,16 @@ class ForwardPlan:
             projs.append((et[1], kernels.ProjSpec(
                 w2.stacks[et], self.proj[et], grp.n_rels, -1, rel_map=grp.rel_map,
                 rel_map_max=int(grp.rel_ids.max()) if grp.rel_map is not None else None)))
-        self._layer1 = self._build_layer(x1, h1, True, f32, projs)
+        self._layer1 = self._build_layer(x1, h1, True, f32, projs,
+                                         post={et: w2.stacks[et] for et in self.edge_types if et in self.preproj})
 
         # ---- layer 2: remaining projections in one batched MFMA GEMM launch, then SpMM ----
         gemms, drops = [], []
         self.hdrop: Dict[EdgeType, torch.Tensor] = {}
         for et in self.edge_types:
             grp = dgraph.groups[et]
-            if not grp.n_rels or et in proj_fused or et in self.staged_proj or et in self.seg_proj:
+            if not grp.n_rels or et in proj_fused or et in self.staged_proj or et in self.seg_proj \
+                    or et in self.preproj:
                 continue
             j = et[1]
             W = w2.stacks[et]
@@ -813,6 +830,22 @@ class ForwardPlan:
                 and all(self.g.groups[et].n_chunks == 1 and self.g.groups[et].n_rels > 0
                         and not self.g.groups[et].staged for et in ets)]
 
+    def _preproject_fits(self, keep_sums: bool) -> bool:
+        """L2_PREPROJECT's conditions: a one-GPU forward-only plan whose layers run the wave-table
+        fused form, with a wave slot in layer 1's workgroups for every (row, sourced relation)."""
+        if not (L2_PREPROJECT and self.fused_seg and WAVE_TABLE and not keep_sums and self.drop_state is None
+                and self.shard is None):
+            return False
+        order = list(self.targets)
+        if any(et[1] not in self.targets for et in self.edge_types):
+            return False
+        if any(len(self.targets[i]) > 64 // (self.h1 // 4) for i in order):  # (_tab_groups_fit, both layers)
+            return False
+        rels = {et: self.g.groups[et].n_rels for et in self.edge_types}
+        waves_t = [sum(rels[et] for et in self.targets[i]) for i in order]
+        sourced_t = [sum(k for et, k in rels.items() if et[1] == i) for i in order]
+        return kernels.tab_proj_fit(waves_t, sourced_t, _tab_balance(self.h1, self.h1), L2_PREPROJECT_SHARE)
+
     def _spec(self, et, x: torch.Tensor, out, d) -> kernels.RelGroupSpec:
         grp = self.g.groups[et]
         return kernels.RelGroupSpec(grp.rowptr, grp.vcol, grp.val, x, out, grp.n_rows, grp.n_chunks, d,
@@ -832,7 +865,8 @@ class ForwardPlan:
         grp = self.g.groups[et]
         return grp.seg2[5] if (grp.seg is None and grp.seg2 is not None) else grp.n_chunks
 
-    def _build_layer(self, xs: Dict[EdgeType, torch.Tensor], d, relu, f32, projs=(), staged_proj=None, seg_w=None):
+    def _build_layer(self, xs: Dict[EdgeType, torch.Tensor], d, relu, f32, projs=(), staged_proj=None, seg_w=None,
+                     post=None):
         """Prepared launches of one layer: fused targets in one dg_gcn_fused_f32 launch; the
         other targets' groups in partial mode + epilogue — with, when sharded, the chunk
         reduce into the all-reduce buffer and the all-reduce before the epilogue."""
@@ -878,6 +912,16 @@ class ForwardPlan:
             d_in = self.h1 if seg_w else d
             if WAVE_TABLE and d_in == 64 and (d == 64 or seg_w) and _tab_groups_fit(tgts, d):
                 # the wave-table form: the same rows bitwise, fewer dependent loads a wave
+                # (post: layer 1 also projecting its rows onto layer 2's relations, L2_PREPROJECT)
+                pj = []
+                for et, W2 in (post or {}).items():
+                    grp = g.groups[et]
+                    pj.append(kernels.TabProjSpec(fused_t.index(et[1]), W2, self.proj[et], grp.n_rels,
+                                                  None if grp.rel_map is None else grp.rel_map.cpu().numpy()))
+                launches.append(kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d), projs=pj,
+                                                         share_proj=L2_PREPROJECT_SHARE))
+            elif WAVE_TABLE and self.preproj and d_in == d == 32 and _tab_groups_fit(tgts, d):
+                # layer 2 over the P stacks layer 1 made: layer 1's shape at half the width
                 launches.append(kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d)))
             else:
                 launches.append(kernels.PreparedFusedSeg(tgts, d_in, d))
@@ -1226,6 +1270,17 @@ class ForwardPlan:
                 for pj in launch._keep[2]:
                     K, din, dout = pj.w.shape
                     tot += 4 * pj.n_rels * (din * dout + pj.out.shape[1] * dout)
+            if layer == 1:
+                tot += self._post_bytes(launch)
+        return tot
+
+    @staticmethod
+    def _post_bytes(launch) -> int:
+        """W2 slabs read once and P rows written once by a projecting layer-1 launch."""
+        tot = 0
+        for pj in getattr(launch, "projs", ()):
+            K, din, dout = pj.w.shape
+            tot += 4 * pj.n_rels * (din * dout + pj.out.shape[1] * dout)
         return tot
 
     def layer_bytes(self, layer: int) -> int:
@@ -1257,6 +1312,7 @@ class ForwardPlan:
                         K, din, dout = pj.w.shape
                         rows = pj.out.shape[1]
                         tot += 4 * pj.n_rels * (din * dout + rows * dout)
+                tot += self._post_bytes(f)
         return tot
 
 

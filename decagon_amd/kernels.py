@@ -335,8 +335,9 @@ class PreparedFusedSeg:
 class _WaveTable:
     """Host builder of a dg_wave_table (decagon_hip.h): per wave slot a 64-byte descriptor and
     the first S pairs of its segment (in the hand-out order of its gather form: pair m in lane
-    16·(m & 3) + (m >> 2), stored compactly at (m & 3)·S/4 + (m >> 2)), the rest in batches of
-    64 in an overflow array.  S (slot_pairs, round 6) is the smallest of 16 / 32 / 48 / 64
+    16·(m & 3) + (m >> 2), stored compactly at (m & 3)·S/4 + (m >> 2); with 32-float rows, lp = 8,
+    eight pairs are handed out at once: lane 8·(m & 7) + (m >> 3), stored at (m & 7)·S/8 + (m >> 3)),
+    the rest in batches of 64 in an overflow array.  S (slot_pairs, round 6) is the smallest of 16 / 32 / 48 / 64
     holding the first batch of ≥ SLOT_COVER of the non-empty waves: a wave then fetches S·8 B
     where round 5 fetched 512 B whatever its length (a config-S wave holds 7–81 pairs)."""
 
@@ -345,9 +346,10 @@ class _WaveTable:
     DESC = np.dtype([("x", "<u8"), ("w", "<u8"), ("orow", "<u8"), ("cnt", "<i4"), ("x_ld", "<i4"), ("ovf", "<i4"),
                      ("role", "<u4"), ("wr", "<u4"), ("pad", "<i4", 5)])
 
-    def __init__(self, specs: Sequence[SegSpec], n_slots: int, proj: bool):
-        assert self.DESC.itemsize == 64
+    def __init__(self, specs: Sequence[SegSpec], n_slots: int, proj: bool, lp: int = 16):
+        assert self.DESC.itemsize == 64 and lp in (8, 16) and not (proj and lp == 8)
         self.specs, self.proj = list(specs), proj
+        self.G = 64 // lp  # pairs handed out at once
         self.host = [(s.rowptr.cpu().numpy(), s.seg.cpu().numpy(), s.vcol.cpu().numpy(), s.val.cpu().numpy(),
                       None if s.slab is None else s.slab.cpu().numpy()) for s in specs]
         self.n_slots = n_slots
@@ -355,7 +357,7 @@ class _WaveTable:
         self.desc = np.zeros(n_slots, self.DESC)
         # entry of pair m within a batch: its lane in the DPP hand-out (both layers since round 6)
         m = np.arange(64)
-        self.lane_of = 16 * (m & 3) + (m >> 2)
+        self.lane_of = (64 // self.G) * (m % self.G) + m // self.G
 
     def bounds(self, g: int, k: int, r: int) -> Tuple[int, int]:
         """[beg, end) of relation k's segment (of spec g) in row r."""
@@ -419,7 +421,7 @@ class _WaveTable:
         ovf: List[np.ndarray] = []
         n_ovf = 0
         m = np.arange(S)
-        compact = (m & 3) * (S // 4) + (m >> 2)  # slot entry of pair m (its lane's row-major rank)
+        compact = (m % self.G) * (S // self.G) + m // self.G  # slot entry of pair m (its lane's row-major rank)
         for i, pv in self.pv.items():
             cnt = len(pv)
             m0 = min(cnt, S)
@@ -455,12 +457,73 @@ def _tab_shape(d_in: int, d_out: int, specs) -> bool:
     return d_in == 64 and (d_out == 64 or (d_out == 32 and all(s.w is not None for s in specs)))
 
 
+@dataclass
+class TabProjSpec:
+    """Projection jobs of a 64 -> 64 PreparedFusedTab launch (layer 1), one spec per edge type
+    sourced from a target's node type: for every row r of target `target` and every local
+    relation k, out[slab(k), r] = H1[r] · w[slab(k)] — layer 2's operand P_k, made in the
+    workgroup that finishes the H1 row (dg_gcn_fused_tab_post_f32)."""
+
+    target: int                   # index into the launch's targets: the rows projected
+    w: torch.Tensor               # float32 [K, 64, 32]
+    out: torch.Tensor             # float32 [K, n_rows, 32]
+    n_rels: int
+    slab: Optional[Sequence[int]] = None  # relation k -> slab (None: slab k)
+
+
+def _tab_geometry(waves_t: Sequence[int], balance: bool) -> Tuple[int, int, List[int]]:
+    """(waves per workgroup, wave-slot stride, rows per workgroup of each target) of a wave-table
+    fused launch whose target t has waves_t[t] relations a row."""
+    nw = max([1] + list(waves_t))
+    stride = 8 if nw <= 8 else 16
+    if balance:
+        nw = stride  # every wave slot of a workgroup takes a share of its rows' pairs
+    return nw, stride, [min(nw // max(1, w), 4) for w in waves_t]
+
+
+def _proj_jobs(rows_present: Sequence[bool], n_rels: int, nw: int, share: bool = False):
+    """Projection jobs of one workgroup: per wave slot (nw of them) its job (row slots, relation)
+    or None.  The workgroup holds len(rows_present) row slots, each projected onto n_rels
+    relations; a slot without a row (the last workgroup of an odd row count) projects nothing.
+    Every (row, relation) goes to exactly one wave, and a wave holds one relation (one W slice).
+    Without `share` a wave takes one row, so no wave takes two (row, relation) jobs; with it, one
+    wave projects every present row onto its relation, so the relation's W slab is read once a
+    workgroup, not once a row.  The waves that do not finish a row (slots rpb .. nw-1: idle while
+    the finishing waves 0 .. rpb-1 work) are filled first.  None when the jobs of a full workgroup
+    (rows per workgroup × relations; with `share`, the relations) exceed nw: the form is not built."""
+    rpb = len(rows_present)
+    if (n_rels if share else rpb * n_rels) > nw:
+        return None
+    jobs: List[Optional[Tuple[Tuple[int, ...], int]]] = [None] * nw
+    order = list(range(rpb, nw)) + list(range(min(rpb, nw)))
+    present = tuple(slot for slot in range(rpb) if rows_present[slot])
+    if share:
+        todo = [(present, k) for k in range(n_rels)] if present else []
+    else:
+        todo = [((slot,), k) for slot in present for k in range(n_rels)]
+    for w, job in zip(order, todo):
+        jobs[w] = job
+    return jobs
+
+
+def tab_proj_fit(waves_t: Sequence[int], sourced_t: Sequence[int], balance: bool, share: bool = False) -> bool:
+    """Whether a wave-table launch whose target t has waves_t[t] relations a row has a wave slot
+    for every projection job: rows per workgroup × sourced_t[t] relations projected per row (with
+    `share`: sourced_t[t] jobs a workgroup)."""
+    nw, _, rpbs = _tab_geometry(waves_t, balance)
+    return all(_proj_jobs([True] * rpb, k, nw, share) is not None for rpb, k in zip(rpbs, sourced_t))
+
+
 class PreparedFusedTab(PreparedFusedSeg):
     """The same launch as PreparedFusedSeg (same targets, rows, waves and arithmetic: bitwise the
     same rows) through dg_gcn_fused_tab_f32: the wave table — each wave's 64-byte descriptor and
     its segment's first 64 pairs at a fixed slot — is built here once, on the host, from the
     chunk-merged CSR and segment starts of the specs (decagon_hip.h documents the layout).
-    Shapes: d_in = d_out = 64, or 64 -> 32 with weight stacks.  peer = (PeerExchange, slot):
+    Shapes: d_in = d_out = 64, 64 -> 32 with weight stacks, or d_in = d_out = 32 (one GPU: no peer
+    form).  projs (TabProjSpec, d_in = d_out = 64, no peer): the launch also makes layer 2's
+    operands from the rows it finishes (dg_gcn_fused_tab_post_f32); seg_form() then still runs the
+    plain seg launch, which writes the rows only.  share_proj: one wave projects every row of
+    its workgroup onto its relation (_proj_jobs).  peer = (PeerExchange, slot):
     the rows also go to every peer and the launch ends with the exchange
     (dg_gcn_fused_tab_peer_f32; PreparedFusedSeg's peer form, bitwise the same rows).
 
@@ -473,25 +536,36 @@ class PreparedFusedTab(PreparedFusedSeg):
     and its finishing roles are unchanged — a group's normalising wave sums its waves' rows in
     order — so only the fp32 summation order within a group differs from the per-relation form."""
 
-    def __init__(self, targets, d_in: int, d_out: int, peer=None, balance: bool = False):
+    def __init__(self, targets, d_in: int, d_out: int, peer=None, balance: bool = False,
+                 projs: Sequence[TabProjSpec] = (), share_proj: bool = True):
         super().__init__(targets, d_in, d_out, peer=peer)
         specs = self._keep[0]
-        if not _tab_shape(d_in, d_out, specs):
-            raise ValueError("dg_gcn_fused_tab_f32: d_in = d_out = 64, or 64 -> 32 with weight stacks")
+        narrow = d_in == d_out == 32 and all(s.w is None for s in specs) and peer is None
+        if not (_tab_shape(d_in, d_out, specs) or narrow):
+            raise ValueError("dg_gcn_fused_tab_f32: d_in = d_out = 64, 64 -> 32 with weight stacks, or "
+                             "d_in = d_out = 32 without an exchange")
         proj = d_out != d_in
         if any(len(gs) > 64 // (d_out // 4) for _, _, gs, _ in targets):
             raise ValueError("dg_gcn_fused_tab_f32: at most 64 / (d_out / 4) groups a target (one lane set each)")
+        self.projs = list(projs)
+        if self.projs and (d_in != 64 or d_out != 64 or peer is not None):
+            raise ValueError("dg_gcn_fused_tab_post_f32: projection jobs follow a 64 -> 64 layer without an exchange")
+        for pj in self.projs:
+            _dev(pj.w, torch.float32, "w")
+            _dev(pj.out, torch.float32, "P")
+            K, rows = pj.w.shape[0], targets[pj.target][1]
+            slabs = list(range(pj.n_rels)) if pj.slab is None else [int(x) for x in pj.slab[:pj.n_rels]]
+            if (tuple(pj.w.shape[1:]) != (64, 32) or tuple(pj.out.shape) != (K, rows, 32) or len(slabs) != pj.n_rels
+                    or any(not 0 <= x < K for x in slabs) or pj.out.data_ptr() % 16 or pj.w.data_ptr() % 16):
+                raise ValueError("projection jobs: w [K, 64, 32], P [K, target rows, 32], slabs inside both")
         waves_t = [sum(s.n_rels for s in gs) for _, _, gs, _ in targets]
-        nw = max([1] + waves_t)
-        stride = 8 if nw <= 8 else 16
-        if balance:
-            nw = stride  # every wave slot of a workgroup takes a share of its rows' pairs
+        nw, stride, rpbs = _tab_geometry(waves_t, balance)
         self.balance = balance
         plan = []  # (target, first row, rows per workgroup) per workgroup, in launch order
         for t, (_, n_rows, _, _) in enumerate(targets):
-            rpb = min(nw // waves_t[t], 4)
+            rpb = rpbs[t]
             plan += [(t, r0, rpb) for r0 in range(0, n_rows, rpb)]
-        tb = _WaveTable(specs, len(plan) * stride, proj)
+        tb = _WaveTable(specs, len(plan) * stride, proj, lp=d_in // 4)
         g_first = np.cumsum([0] + [len(gs) for _, _, gs, _ in targets])
         for b, (t, r0, rpb) in enumerate(plan):
             out, n_rows, gspecs, relu = targets[t]
@@ -532,12 +606,34 @@ class PreparedFusedTab(PreparedFusedSeg):
                     tb.desc["pad"][i, 2] = np.int32(np.uint32(sum((c - 1) << (4 * u)
                                                                   for u, c in enumerate(counts[w]))))
                     tb.desc["pad"][i, 3] = w * per_row
+            # projection jobs (role bit 30, the job's row slots in bits 24-27): W2_k in `w`, the
+            # address of row slot 0's P row in pad[0..1] (the peer form's fields: a projecting
+            # launch has no exchange)
+            rels = [(pj, k) for pj in self.projs if pj.target == t for k in range(pj.n_rels)]
+            if rels:
+                jobs = _proj_jobs([r0 + slot < n_rows for slot in range(rpb)], len(rels), nw, share_proj)
+                if jobs is None:
+                    raise ValueError(f"{rpb} rows x {len(rels)} projection jobs for {nw} wave slots")
+                for w, job in enumerate(jobs):
+                    if job is None:
+                        continue
+                    slots, (pj, k) = job[0], rels[job[1]]
+                    sl = k if pj.slab is None else int(pj.slab[k])
+                    i = b * stride + w
+                    addr = pj.out.data_ptr() + (sl * n_rows + r0) * 32 * 4
+                    tb.desc["role"][i] |= np.uint32((1 << 30) | (sum(1 << x for x in slots) << 24))
+                    tb.desc["w"][i] = pj.w.data_ptr() + sl * 64 * 32 * 4
+                    tb.desc["pad"][i, 0] = np.uint32(addr & 0xffffffff).astype(np.int32)
+                    tb.desc["pad"][i, 1] = np.uint32(addr >> 32).astype(np.int32)
         if not plan and peer is not None:
             raise ValueError("dg_gcn_fused_tab_peer_f32: the exchange needs at least one row a rank")
         self._tab = tb.upload(self, len(plan), nw, stride, specs[0].x.device)
         self.n_blocks, self.nw = len(plan), nw
         if self._xchg is not None:
             self._tfn, self._tname = _lib.load().dg_gcn_fused_tab_peer_f32, "dg_gcn_fused_tab_peer_f32"
+        elif self.projs:
+            self._keep = self._keep + (self.projs,)
+            self._tfn, self._tname = _lib.load().dg_gcn_fused_tab_post_f32, "dg_gcn_fused_tab_post_f32"
         else:
             self._tfn, self._tname = _lib.load().dg_gcn_fused_tab_f32, "dg_gcn_fused_tab_f32"
 

@@ -235,28 +235,40 @@ int dg_gcn_fused_seg_f32(const dg_seg_group* groups /* HOST */, int32_t n_groups
                          const dg_fused_target* targets /* HOST */, int32_t n_targets, int32_t d_in,
                          int32_t d_out, void* stream);
 
-/* The wave-table form of dg_gcn_fused_seg_f32 (round 5): the same launch — workgroups, waves,
- * arithmetic and summation order, so bitwise the same rows — with everything a wave needs
- * before its gathers precomputed on the host (decagon_amd/sparse.py: wave_table) instead of
- * found at run time from the group and target arguments.  Wave w of workgroup b (slot
- * i = b * nw_stride + w) reads desc[i] and the first batch of its relation segment's pairs,
- * pairs[64 i .. 64 i + 63] (vcol, fp32 value bits: int32 pairs), in one round trip; a segment
- * longer than 64 continues in ovf[desc[i].ovf ..] in batches of 64.  Within a batch, pair
- * m of a d_in = 64, d_out = 64 table sits in entry 16 (m & 3) + (m >> 2) (the DPP hand-out
- * order of the seg form), of a d_in = 64, d_out = 32 table (layer 2 reassociated) in entry m.
- * A wave with cnt 0 gathers nothing; desc.role (active << 31 | nbuf slot << 16 | K << 8 | first
- * wave) makes it the wave that sums and L2-normalises one (row slot, group); desc.orow != NULL
- * makes it the writer of that output row (wr = group count | relu << 8 | row slot << 16).
- * Shapes: d_in = d_out = 64, or d_in = 64, d_out = 32 with W slabs (desc.w).  Replaces
- * layers.py:85-94 / 109-118 and model.py:74-75, 85-88 as dg_gcn_fused_seg_f32 does. */
+/* The wave-table form of dg_gcn_fused_seg_f32 (round 5): the same launch — workgroups, waves and
+ * arithmetic — with everything a wave needs before its gathers precomputed on the host
+ * (decagon_amd/kernels.py: _WaveTable, PreparedFusedTab) instead of found at run time from the
+ * group and target arguments.  Wave w of workgroup b (slot i = b * nw_stride + w) reads desc[i]
+ * and the first batch of its pairs (vcol, fp32 value bits: int32 pairs) in one round trip: the
+ * first batch is compact, the S = slot_pairs pairs at pairs[S i .. S i + S - 1]; a wave with
+ * more than S pairs continues in ovf[desc[i].ovf ..] in batches of 64.  Every shape uses the DPP
+ * hand-out order of the seg form (both layers since round 6): with G = 256 / (4 d_in) pairs
+ * handed out at once (4 at d_in 64, 8 at d_in 32), pair m < S of the wave sits at slot entry
+ * (m % G) * S/G + m / G, and pair j of a later batch at entry (64/G) * (j % G) + j / G.
+ * A wave with cnt 0 gathers nothing.  The wave whose desc.orow != NULL finishes that output row
+ * alone after the workgroup's barrier: wr = group count | relu << 8 | row slot << 16,
+ * pad[2] = (wave count - 1) of group u in bits 4u .. 4u + 3, pad[3] = the row slot's first wave;
+ * it adds each group's waves in order, L2-normalises the group sums, adds them in order, applies
+ * relu and stores the row.  The rows are bitwise dg_gcn_fused_seg_f32's only for a table with one
+ * wave per relation; a table that deals a group's pairs over several waves (PreparedFusedTab's
+ * balance) re-associates the group's fp32 sum.  desc.role is not read by dg_gcn_fused_tab_f32 or
+ * its peer form (the host builder still records the round-5 normalising role in bits 0-20 and 31);
+ * dg_gcn_fused_tab_post_f32 reads bits 24-27 and 30, and dg_spmm_seg_tab_f32 bits 8-15, as described
+ * with them.  pad[0..1] belong to the peer form (below) or, in a projecting table, hold the P
+ * row's address; pad[4] is unused.
+ * Shapes: d_in = d_out = 64; d_in = 64, d_out = 32 with W slabs (desc.w: the aggregate times the
+ * relation's slab, so such a wave holds pairs of one relation); d_in = d_out = 32 (no exchange
+ * form).  Replaces layers.py:85-94 / 109-118 and model.py:74-75, 85-88 as dg_gcn_fused_seg_f32
+ * does. */
 typedef struct dg_tab_desc {
     const float* x;       /* device: gather base (vcol * x_ld floats from here)             */
-    const float* w;       /* device: the relation's W slab [64][32] (d_out 32), or NULL      */
-    float* orow;          /* device: the output row this wave writes, or NULL               */
-    int32_t cnt;          /* pairs of the wave's segment (0: none)                          */
+    const float* w;       /* device: the wave's W slab [64][32] (d_out 32, or a projection   */
+                          /* job of dg_gcn_fused_tab_post_f32), or NULL                      */
+    float* orow;          /* device: the output row this wave finishes and writes, or NULL  */
+    int32_t cnt;          /* pairs of the wave (0: none)                                     */
     int32_t x_ld;         /* floats                                                          */
     int32_t ovf;          /* first entry of the later batches in ovf                         */
-    uint32_t role;
+    uint32_t role;        /* see above                                                       */
     uint32_t wr;
     int32_t pad[5];
 } dg_tab_desc;            /* 64 bytes                                                        */
@@ -269,12 +281,24 @@ typedef struct dg_wave_table {
     int32_t nw;           /* waves per workgroup, 1..16                                      */
     int32_t nw_stride;    /* 8 if nw <= 8, else 16                                           */
     int32_t slot_pairs;   /* S: pairs of a wave's first batch, 16 / 32 / 48 / 64 (ABI 37;     */
-                          /* 0 means 64): pair m < S of the segment at slot entry             */
-                          /* (m & 3)·S/4 + (m >> 2); pairs S, S+1, ... in batches of 64 from  */
-                          /* ovf + desc.ovf, pair j of a batch at entry 16·(j & 3) + (j >> 2) */
+                          /* 0 means 64), laid out as described above                         */
 } dg_wave_table;
 
 int dg_gcn_fused_tab_f32(const dg_wave_table* table /* HOST */, int32_t d_in, int32_t d_out, void* stream);
+
+/* dg_gcn_fused_tab_f32 for a d_in = d_out = 64 table that also carries projection jobs: layer 1
+ * makes layer 2's operands P_k = H1_j·W2_k (layers.py:113, the reference's own order: matmul,
+ * then the sparse product) in the workgroup that finishes the H1 row.  The finishing wave also
+ * leaves its row (after relu, as stored) in LDS; after one more barrier every wave whose
+ * desc.role has bit 30 set multiplies the row of each row slot s in the mask (role >> 24) & 15
+ * by the [64][32] slab at desc.w and stores the 32 floats at A + 128 s bytes, A the 16-byte
+ * aligned address in pad[0] (low half) and pad[1] (high half): row slot 0's P row (the rows of a
+ * workgroup are consecutive).  A wave may hold a gather job, a projection job, both or neither; a
+ * job names only row slots whose finishing wave exists in the same workgroup.  The H1 rows are
+ * bitwise dg_gcn_fused_tab_f32's of the same table.  The table itself cannot say that it carries
+ * jobs, hence the separate entry point; arguments are checked as dg_gcn_fused_tab_f32's, and
+ * only d_in = d_out = 64 is accepted. */
+int dg_gcn_fused_tab_post_f32(const dg_wave_table* table /* HOST */, int32_t d_in, int32_t d_out, void* stream);
 
 /* dg_gcn_fused_tab_f32 with the peer-store exchange (config S at N = 2 with --exchange peer):
  * every finished row also goes to every peer's copy of its target — desc.pad[0] = the row's

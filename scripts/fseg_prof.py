@@ -65,8 +65,15 @@ def main():
                    "'search' is its first round trip (descriptor + first 64 pairs); in layer 2 'bounds' "
                    "is its gathers (first pairs in registers -> aggregate folded) and 'relation' the "
                    "projection by W2_k (W slice load, LDS hand-off, FMAs, butterfly); 'normalise' is the "
-                   "finishing wave's group sums, norms and cross-group sum (no second barrier since round 6)",
+                   "finishing wave's group sums, norms and cross-group sum (no second barrier since round 6). "
+                   "With DG_L2_PREPROJECT (the default) layer 2 is the plain 32-wide form: its 'bounds' is "
+                   "empty and 'relation' its gathers; layer 1's 'relation' then ends with the issue of the "
+                   "projecting waves' W slice loads and the profiling build's wait for them, and its 'store' "
+                   "(finishing waves only) runs to the second barrier",
            "launches": {}}
+    l1, l2 = (L[0] for L in plan.spmm_launches)
+    l1_name = "layer1 (projecting tail)" if getattr(l1, "projs", None) else "layer1"
+    l2_name = "layer2 (reassociated)" if l2.d_in != l2.d_out else "layer2 (32-wide gather over P)"
     bufs = {}
     for proj in (0, 1):
         buf = np.zeros((4096, 16, 8), np.uint64)
@@ -93,7 +100,7 @@ def main():
             ph[nm] = {"median_us": float(np.median(d)), "p90_us": float(np.percentile(d, 90)),
                       "max_us": float(d.max())}
         xcc = buf[blocks, 0, 7].astype(int)
-        out["launches"]["layer2 (reassociated)" if proj else "layer1"] = {
+        out["launches"][l2_name if proj else l1_name] = {
             "workgroups": int(len(blocks)),
             "start_us_after_first_layer1_wave": (k0 - t_ref) * 0.01,
             "span_us": (k1 - k0) * 0.01,
