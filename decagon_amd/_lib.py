@@ -219,6 +219,7 @@ SIGNATURES = {
                                            c_void_p]),
     "dg_gcn_fused_tab_f32": (c_int32, [POINTER(DgWaveTable), c_int32, c_int32, c_void_p]),
     "dg_gcn_fused_tab_post_f32": (c_int32, [POINTER(DgWaveTable), c_int32, c_int32, c_void_p]),
+    "dg_gcn_fused_tab_dec_f32": (c_int32, [POINTER(DgWaveTable), c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "dg_gcn_fused_tab_peer_f32": (c_int32, [POINTER(DgWaveTable), c_int32, c_int32, POINTER(DgPeerXchg), c_void_p]),
     "dg_spmm_seg_tab_f32": (c_int32, [POINTER(DgWaveTable), c_int32, c_int32, c_void_p]),
     "dg_gcn_epilogue_tab_f32": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(DgPeerXchg), c_void_p]),
@@ -265,6 +266,12 @@ SIGNATURES = {
         [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
          c_uint64, c_uint64, c_int32, c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p,
          c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
+    "dg_decoder_hinge_rows_f32": (
+        c_int32,
+        [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+         c_uint64, c_uint64, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p],
     ),
     "dg_decoder_score_f32": (
         c_int32,

@@ -199,6 +199,155 @@ __global__ __launch_bounds__(128) void decoder_hinge_kernel(const HingeArgs a) {
     }
 }
 
+// The fused decoder step over row operands (dg_decoder_hinge_rows_f32, d = 32): with
+// Q[r] = l ∘ ((E[r] ∘ l)·G) stored per row by the launch that finished E (segspmm.hip, DEC),
+// score(r, c) = Q[r]·E[c] — no G loads, no MFMA chain, no reduce-scatter.  Eight lanes a pair:
+// lane q of the group reads float4 q of E[c], Q[r] and Q[neg] (the positive and the negative
+// share the column row), folds both dots over the group and forms the hinge term in-lane.  A
+// wave holds 8·PPG pairs (pair g + 8u of the workgroup's in lane group g, u < PPG, every load in
+// flight together), a workgroup NW waves.  Draws, outputs and the hand-off are
+// decoder_hinge_kernel's: the same counters, PACKED's one returning atomic per workgroup, or
+// the sc1 partial + ticket above 255 workgroups.
+struct RowsHingeArgs {
+    const float* Q;
+    const float* col_table;
+    int64_t ld_q;
+    int64_t ld_col;
+    const int32_t* rows;
+    const int32_t* cols;
+    const int32_t* neg_given;
+    const uint2* alias;
+    float* pos;
+    float* neg;
+    int32_t* neg_rows_out;
+    float* loss;
+    float* partial;
+    uint32_t* ticket;
+    unsigned long long* word;
+    uint64_t seed;
+    uint64_t offset;
+    int32_t range;
+    int32_t n;
+    float margin;
+};
+
+__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
+    return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)));
+}
+
+template <bool PACKED, int NW, int PPG>
+__global__ __launch_bounds__(64 * NW) void decoder_rows_hinge_kernel(const RowsHingeArgs a) {
+    __shared__ float wsum[NW];
+    __shared__ int last;
+    __shared__ unsigned long long total;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int g = lane >> 3, q = lane & 7;
+    const int b0 = (blockIdx.x * NW + wave) * (8 * PPG) + g;
+    int ridx[PPG], nidx[PPG], cidx[PPG];
+#pragma unroll
+    for (int u = 0; u < PPG; ++u) {
+        const int b = b0 + 8 * u;
+        ridx[u] = nidx[u] = cidx[u] = 0;
+        if (b < a.n) {
+            cidx[u] = a.cols[b];
+            ridx[u] = a.rows[b];
+            nidx[u] = a.neg_given ? a.neg_given[b] : unigram_draw(a.alias, a.range, a.seed, a.offset + (uint64_t)b);
+        }
+    }
+    float4 ev[PPG], qp[PPG], qn[PPG];
+#pragma unroll
+    for (int u = 0; u < PPG; ++u) {  // (pairs past the end read row 0: in bounds, never used)
+        ev[u] = *reinterpret_cast<const float4*>(a.col_table + (int64_t)cidx[u] * a.ld_col + 4 * q);
+        qp[u] = *reinterpret_cast<const float4*>(a.Q + (int64_t)ridx[u] * a.ld_q + 4 * q);
+        qn[u] = *reinterpret_cast<const float4*>(a.Q + (int64_t)nidx[u] * a.ld_q + 4 * q);
+    }
+    float term = 0.f;
+#pragma unroll
+    for (int u = 0; u < PPG; ++u) {
+        const int b = b0 + 8 * u;
+        float sp = dot4(qp[u], ev[u]), sn = dot4(qn[u], ev[u]);
+        sp = dg::xor_add<1>(dg::xor_add<2>(dg::xor_add<4>(sp)));
+        sn = dg::xor_add<1>(dg::xor_add<2>(dg::xor_add<4>(sn)));
+        if (b < a.n) {
+            if (q == 0) {
+                a.pos[b] = sp;
+                a.neg[b] = sn;
+                if (a.neg_rows_out) a.neg_rows_out[b] = nidx[u];
+            }
+            term += fmaxf(sn - (sp - a.margin), 0.f);  // (pairs u = 0, 1, ... in order)
+        }
+    }
+    // the wave's pairs: every lane of a group holds its term; the groups add up in a fixed order
+    term = dg::xor_add<32>(dg::xor_add<16>(dg::xor_add<8>(term)));
+    if constexpr (NW > 1) {
+        if (lane == 0) wsum[wave] = term;
+        __syncthreads();
+        term = wsum[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) {
+            // (an opaque copy: the compiler otherwise folds the pair with a packed add whose low
+            // result reads src1's high half, the form kept out of this library — DESIGN.md §5)
+            float t = wsum[w];
+            asm volatile("" : "+v"(t));
+            term += t;
+        }
+    }
+    if (threadIdx.x == 0) {
+        if constexpr (PACKED) {
+            unsigned long long add = 1ull << 56;
+            if (term < 256.0f) {  // (false for NaN and inf too)
+                add += static_cast<unsigned long long>(static_cast<double>(term) * 4294967296.0 + 0.5);  // nearest
+            } else {
+                __hip_atomic_store(a.partial + blockIdx.x, term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                add += 1ull << 48;
+            }
+            const unsigned long long old =
+                __hip_atomic_fetch_add(a.word, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = (old >> 56) == gridDim.x - 1 ? 1 : 0;
+            total = old + add;
+        } else {  // (decoder_hinge_kernel's hand-off: sc1 partial, drained, then the ticket)
+            __hip_atomic_store(a.partial + blockIdx.x, term, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const uint32_t t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = (t == gridDim.x - 1) ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    if (!last) return;  // block-uniform
+    if constexpr (PACKED) {
+        if (threadIdx.x == 0) {
+            double s = static_cast<double>(total & ((1ull << 48) - 1)) * (1.0 / 4294967296.0);
+            if ((total >> 48) & 0xFF) {  // partials outside the fixed-point range, in block order
+                for (int k = 0; k < (int)gridDim.x; ++k) {
+                    const float v = __hip_atomic_load(a.partial + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (v != 0.f) {
+                        s += static_cast<double>(v);
+                        __hip_atomic_store(a.partial + k, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+            }
+            a.loss[0] = static_cast<float>(s);
+            __hip_atomic_store(a.word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return;
+    }
+    if (wave != 0) return;
+    // wave 0 of the last workgroup: lane t adds partials t, t + 64, ... in order, then the lanes
+    // fold in a fixed order; every partial read is reset for the next launch
+    float s = 0.f;
+    for (int k = lane; k < (int)gridDim.x; k += 64) {
+        s += __hip_atomic_load(a.partial + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        a.partial[k] = 0.f;
+    }
+    s = dg::xor_add<32>(dg::xor_add<16>(dg::xor_add<8>(dg::xor_add<4>(dg::xor_add<2>(dg::xor_add<1>(s))))));
+    if (lane == 0) {
+        a.loss[0] = s;
+        atomicExch(a.ticket, 0u);
+    }
+}
+
 // Fixed-order block reduction (deterministic): thread t sums t, t+256, ... then a tree.
 template <typename F>
 __device__ float block_sum_256(int n, F term) {
@@ -401,5 +550,60 @@ extern "C" int dg_decoder_hinge_f32(const float* row_table, int64_t ld_row, cons
     else
         hipLaunchKernelGGL(decoder_hinge_kernel<false>, dim3(blocks), dim3(128), 0,
                            reinterpret_cast<hipStream_t>(stream), a);
+    return dg::launch_status();
+}
+
+// Workgroup geometry of the row-operand decoder: waves a workgroup and pairs a lane group
+// (DESIGN.md §5 has the measurements).  DG_DEC_ROWS_PAIRS in decagon_hip.h is their product · 8.
+#ifndef DG_DEC_ROWS_NW
+#define DG_DEC_ROWS_NW 2
+#endif
+#ifndef DG_DEC_ROWS_PPG
+#define DG_DEC_ROWS_PPG 1
+#endif
+static_assert(DG_DEC_ROWS_NW * DG_DEC_ROWS_PPG * 8 == DG_DEC_ROWS_PAIRS, "decagon_hip.h: pairs a workgroup");
+
+extern "C" int dg_decoder_hinge_rows_f32(const float* Q, int64_t ld_q, const float* col_table, int64_t ld_col,
+                                         const int32_t* rows, const int32_t* cols, const int32_t* neg_rows,
+                                         const uint32_t* alias_table, int32_t range, uint64_t seed,
+                                         uint64_t offset, int32_t n, int32_t d, float margin, float* pos,
+                                         float* neg, int32_t* neg_rows_out, float* loss, void* workspace,
+                                         void* stream) {
+    if (n < 1 || d != 32) return DG_EINVAL;
+    if (!Q || !col_table || !rows || !cols || !pos || !neg || !loss || !workspace) return DG_EINVAL;
+    if (!neg_rows && (!alias_table || range < 1)) return DG_EINVAL;
+    if (ld_q < d || ld_col < d) return DG_EINVAL;
+    if (!dg::aligned16(workspace) || !dg::aligned16(Q) || !dg::aligned16(col_table) || (ld_q & 3) || (ld_col & 3))
+        return DG_EALIGN;
+    const int blocks = dg::ceil_div(n, DG_DEC_ROWS_PAIRS);
+    RowsHingeArgs a{};
+    a.Q = Q;
+    a.col_table = col_table;
+    a.ld_q = ld_q;
+    a.ld_col = ld_col;
+    a.rows = rows;
+    a.cols = cols;
+    a.neg_given = neg_rows;
+    a.alias = reinterpret_cast<const uint2*>(alias_table);
+    a.pos = pos;
+    a.neg = neg;
+    a.neg_rows_out = neg_rows_out;
+    a.loss = loss;
+    a.ticket = reinterpret_cast<uint32_t*>(workspace);
+    a.word = reinterpret_cast<unsigned long long*>(workspace) + 1;
+    a.partial = reinterpret_cast<float*>(workspace) + 4;
+    a.seed = seed;
+    a.offset = offset;
+    a.range = range;
+    a.n = n;
+    a.margin = margin;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // ≤ 255 workgroups: one returning 64-bit atomic per block (PACKED); more: the sc1 ticket
+    if (blocks <= 255)
+        hipLaunchKernelGGL((decoder_rows_hinge_kernel<true, DG_DEC_ROWS_NW, DG_DEC_ROWS_PPG>), dim3(blocks),
+                           dim3(64 * DG_DEC_ROWS_NW), 0, st, a);
+    else
+        hipLaunchKernelGGL((decoder_rows_hinge_kernel<false, DG_DEC_ROWS_NW, DG_DEC_ROWS_PPG>), dim3(blocks),
+                           dim3(64 * DG_DEC_ROWS_NW), 0, st, a);
     return dg::launch_status();
 }

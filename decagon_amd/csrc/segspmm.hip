@@ -667,13 +667,20 @@ __device__ __forceinline__ float4 load4_global(const float* p) {
 // both gene rows of its workgroup, 5.26 with the loads issued after the first barrier instead —
 // no difference — and 4.87 with the slice not loaded at all: the second barrier, the FMAs and
 // the P store cost 0.6 us, the slabs' L2 -> CU traffic 0.45.)
-template <bool PROJ, int NW, bool PEER, int LP = 16, bool POST = false>
+// DEC (dg_gcn_fused_tab_dec_f32; layer 2, 32 -> 32): the DEDICOM decoder's row operands
+// Q[r] = l ∘ ((E[r] ∘ l)·G) are made here, where the embedding row is born, so a score is the dot
+// product Q[r]·E[c] (decoder.hip, decoder_rows_hinge_kernel).  A finishing wave whose descriptor
+// carries role bit 29 (the Q row's address in pad[0..1]) passes the row it stored to all its lanes
+// through its own ybuf slot and multiplies it by G: no second barrier, the other waves are done.
+template <bool PROJ, int NW, bool PEER, int LP = 16, bool POST = false, bool DEC = false>
 __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restrict__ pairs,
                                                           const dg_tab_desc* __restrict__ desc,
                                                           const uint2* __restrict__ ovf, const int S,
-                                                          const dg::PeerK P) {
+                                                          const dg::PeerK P, const float* __restrict__ decG,
+                                                          const float* __restrict__ decl) {
     static_assert(LP == 16 || (LP == 8 && !PROJ && !PEER), "gcn_tab_kernel: 32-float rows in the plain one-GPU form");
     static_assert(!POST || (LP == 16 && !PROJ && !PEER), "gcn_tab_kernel: the projecting tail follows a 64 -> 64 layer");
+    static_assert(!DEC || (LP == 8 && !POST), "gcn_tab_kernel: the decoder's row operands follow the 32 -> 32 layer");
     constexpr int DOUT4 = PROJ ? 8 : LP;
     [[maybe_unused]] constexpr int kFsForm = (PROJ || LP == 8) ? 1 : 0;
     __shared__ float4 ybuf[NW][16];
@@ -696,17 +703,35 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
     // the branch into a round trip of its own
     asm volatile("" ::"s"(D.x), "s"(D.w), "s"(D.orow), "s"(D.cnt), "s"(D.x_ld), "s"(D.ovf), "s"(D.role), "s"(D.wr),
                  "s"(ovf));
-    if constexpr (POST) asm volatile("" ::"s"(D.pad[0]), "s"(D.pad[1]));
+    if constexpr (POST || DEC) asm volatile("" ::"s"(D.pad[0]), "s"(D.pad[1]));
 #ifdef DG_FSEG_PROF
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #endif
     DG_FS_STAMP(1);  // descriptor and first pairs in registers
     if constexpr (!PROJ) DG_FS_STAMP(2);  // (layer 2: stamp 2 marks its gathers done, in tab_wave)
+    const int ms = lane >> 3;
     const float4 res = tab_wave<PROJ, PROJ ? kTabUP : kTabU, LP>(D, first, ovf, ybuf[wave], S);
+    // DEC: this lane's slice of the decoder's parameters — rows 4(l>>3) .. +4 of G at output float4
+    // l & 7, and l at both — issued here as POST's W slice is, by the flagged finishing waves only
+    // (48 VGPRs as the plain instance; issued before the gather loop instead: 66 VGPRs and the same
+    // 4.27-4.33 µs a launch at config S)
+    const bool djob = DEC && ((D.role >> 29) & 1u) && D.orow != nullptr;  // wave-uniform
+    float4 gv[DEC ? 4 : 1], lin, lout;  // (read only under djob)
+    if constexpr (DEC) {
+        lin = lout = make_float4(1.f, 1.f, 1.f, 1.f);
+        if (djob) {
+            const float* gp = decG + 4 * ((4 * ms) * 8 + (lane & 7));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) gv[i] = load4_global(gp + 4 * 8 * i);
+            if (decl != nullptr) {  // uniform
+                lin = load4_global(decl + 4 * ms);
+                lout = load4_global(decl + 4 * (lane & 7));
+            }
+        }
+    }
     // POST: this lane's slice of the job's W2_k (rows 8(l>>3) .. +8, output float4 l & 7), issued
     // now that the gathers are folded (res) and waited for only after the second barrier
     const bool pjob = POST && ((D.role >> 30) & 1u);  // wave-uniform
-    const int ms = lane >> 3;
     float4 wv[POST ? 8 : 1];  // (read only under pjob)
     if constexpr (POST) {
         if (pjob) {
@@ -759,9 +784,30 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
             }
             reinterpret_cast<float4*>(D.orow)[lane] = tot;
             if constexpr (POST) hbuf[(D.wr >> 16) & (kFsMaxRpb - 1)][lane] = tot;  // the row as stored
+            if constexpr (DEC) ybuf[wave][lane] = tot;  // (this wave's own slot: unused by plain sums)
             if constexpr (PEER)
                 dg::peer_store4(P, reinterpret_cast<const float*>(reinterpret_cast<const char*>(D.orow) - D.pad[0]),
                                 (uint32_t)D.pad[1], (uint32_t)D.pad[0] + 16u * lane, tot);
+        }
+        if constexpr (DEC) {
+            // Q = l ∘ ((e ∘ l)·G) of the row just stored: lane (s, c) = (l >> 3, l & 7) multiplies
+            // e[4s .. 4s+3] ∘ l into its four G rows at output float4 c, the eight s add up in
+            // the butterfly's fixed order, and lanes 0-7 store the 32 floats.  The row is this
+            // wave's own: no second barrier.
+            if (djob) {
+                __builtin_amdgcn_wave_barrier();
+                const float4 e = ybuf[wave][ms];
+                float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+                dg::fma4(z, e.x * lin.x, gv[0]);
+                dg::fma4(z, e.y * lin.y, gv[1]);
+                dg::fma4(z, e.z * lin.z, gv[2]);
+                dg::fma4(z, e.w * lin.w, gv[3]);
+                z = dg::xor_sum4_from<8>(z);
+                if (lane < 8) {
+                    float4* qrow = reinterpret_cast<float4*>(((uint64_t)(uint32_t)D.pad[1] << 32) | (uint32_t)D.pad[0]);
+                    qrow[lane] = make_float4(z.x * lout.x, z.y * lout.y, z.z * lout.z, z.w * lout.w);
+                }
+            }
         }
     }
     if constexpr (POST) {
@@ -1035,13 +1081,15 @@ extern "C" int dg_gcn_fused_seg_f32(const dg_seg_group* groups, int32_t n_groups
 
 namespace {
 int fused_tab_launch(const dg_wave_table* t, int32_t d_in, int32_t d_out, const dg_peer_xchg* xchg, bool post,
-                     void* stream) {
+                     void* stream, bool dec = false, const float* G = nullptr, const float* l = nullptr) {
     if (!t) return DG_EINVAL;
     bool proj = false;
     if (seg_shape(d_in, d_out, proj) != DG_OK) return DG_EINVAL;
     const bool narrow = !proj && d_in == 32;  // the 32 -> 32 instance: one GPU, no exchange
     if (narrow && xchg) return DG_EINVAL;
     if (post && (xchg || proj || d_in != 64)) return DG_EINVAL;  // the projecting tail: after a 64 -> 64 layer
+    if (dec && (!narrow || !G)) return DG_EINVAL;  // the decoder's row operands: after the 32 -> 32 layer
+    if (dec && (!dg::aligned16(G) || !dg::aligned16(l))) return DG_EALIGN;
     if (t->n_blocks < 0 || t->nw < 1 || t->nw > 16 || t->nw_stride != (t->nw <= 8 ? 8 : 16)) return DG_EINVAL;
     if (t->n_blocks == 0) return xchg ? DG_EINVAL : DG_OK;  // (an exchange needs a workgroup a rank)
     if (!t->pairs || !t->desc || !dg::aligned16(t->pairs) || (reinterpret_cast<uintptr_t>(t->desc) & 63))
@@ -1059,8 +1107,11 @@ int fused_tab_launch(const dg_wave_table* t, int32_t d_in, int32_t d_out, const 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     dim3 grid(static_cast<unsigned>(t->n_blocks)), block(64 * t->nw);
 #define DG_TAB_LAUNCH(PR, NWV, PE, ...) \
-    hipLaunchKernelGGL((gcn_tab_kernel<PR, NWV, PE, ##__VA_ARGS__>), grid, block, 0, st, pr, t->desc, ov, S, P)
-    if (narrow) {
+    hipLaunchKernelGGL((gcn_tab_kernel<PR, NWV, PE, ##__VA_ARGS__>), grid, block, 0, st, pr, t->desc, ov, S, P, G, l)
+    if (narrow && dec) {
+        if (t->nw_stride == 8) DG_TAB_LAUNCH(false, 8, false, 8, false, true);
+        else DG_TAB_LAUNCH(false, 16, false, 8, false, true);
+    } else if (narrow) {
         if (t->nw_stride == 8) DG_TAB_LAUNCH(false, 8, false, 8); else DG_TAB_LAUNCH(false, 16, false, 8);
     } else if (post) {
         if (t->nw_stride == 8) DG_TAB_LAUNCH(false, 8, false, 16, true); else DG_TAB_LAUNCH(false, 16, false, 16, true);
@@ -1088,6 +1139,11 @@ extern "C" int dg_gcn_fused_tab_f32(const dg_wave_table* t, int32_t d_in, int32_
 
 extern "C" int dg_gcn_fused_tab_post_f32(const dg_wave_table* t, int32_t d_in, int32_t d_out, void* stream) {
     return fused_tab_launch(t, d_in, d_out, nullptr, true, stream);
+}
+
+extern "C" int dg_gcn_fused_tab_dec_f32(const dg_wave_table* t, int32_t d_in, int32_t d_out, const float* G,
+                                        const float* l, void* stream) {
+    return fused_tab_launch(t, d_in, d_out, nullptr, false, stream, true, G, l);
 }
 
 extern "C" int dg_gcn_fused_tab_peer_f32(const dg_wave_table* t, int32_t d_in, int32_t d_out,

@@ -110,6 +110,10 @@ L2_PREPROJECT = knob("DG_L2_PREPROJECT", True)
 # ... one wave projecting every row of its workgroup onto a relation (the W slab read once a
 # workgroup: config S's layer 1 5.46 -> 5.31 us); 0: one (row, relation) a wave
 L2_PREPROJECT_SHARE = knob("DG_L2_PREPROJECT_SHARE", True)
+# ... and layer 2's launch in turn makes the DEDICOM decoder's row operands
+# Q[r] = l ∘ ((E[r] ∘ l)·G) from the embedding rows it finishes (dg_gcn_fused_tab_dec_f32), for a
+# decoder that attaches (ForwardPlan.attach_decoder_rows; kernels.PreparedDecoderHinge does): a
+# score is then a 32-float dot product.  Read per attachment: DG_DEC_PREPROJECT=0 never attaches.
 STAGED_FIRST = knob("DG_STAGED_FIRST", True)
 # sharded forward plans: layer 2 of the non-staged groups reassociated over the rank's own rows
 # and relations, Σ_k (Â_k·H1_j)·W2_k in dg_spmm_seg_f32, instead of every rank projecting all of
@@ -556,6 +560,9 @@ class ForwardPlan:
         self.keep_sums = keep_sums
         self.sums_mode = False  # set below: partial mode whose epilogue also writes each S_ij
         self.launch_groups: Dict[int, List[EdgeType]] = {}  # id(SpMM launch) -> its groups
+        self.runs = 0     # run() calls so far (decoder_rows_valid)
+        self._dec = None  # the attached decoder's row operands (attach_decoder_rows)
+        self._dec_retired: list = []
         dev = dgraph.device
         f32 = dict(device=dev, dtype=torch.float32)
         self.edge_types = list(dgraph.edge_types)
@@ -694,6 +701,8 @@ class ForwardPlan:
 
         self.hidden1 = {i: out_buf(i, h1, 1) for i in self.targets}
         self.embeddings = {i: out_buf(i, h2, 2) for i in self.targets}
+        for i, e in self.embeddings.items():  # (a decoder built on one finds this plan from the tensor)
+            kernels.register_row_producer(e, self, i)
 
         # ---- layer-2 projection buffers P_k = H1_j·W2_k (global slabs) ----
         # staged groups make their slabs H1_j·W2_k in the layer-2 kernel itself
@@ -923,6 +932,8 @@ class ForwardPlan:
             elif WAVE_TABLE and self.preproj and d_in == d == 32 and _tab_groups_fit(tgts, d):
                 # layer 2 over the P stacks layer 1 made: layer 1's shape at half the width
                 launches.append(kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d)))
+                # (attach_decoder_rows rebuilds this launch with the decoder's row operands)
+                self._l2_tab = (tgts, d_in, d, _tab_balance(d_in, d), list(fused_t), launches[-1])
             else:
                 launches.append(kernels.PreparedFusedSeg(tgts, d_in, d))
             self.launch_groups[id(launches[-1])] = [et for i in fused_t for et in self.targets[i]]
@@ -1195,6 +1206,66 @@ class ForwardPlan:
             self.peer.ensure_ok()  # a timed-out exchange found by an earlier check poisons the plan
         self.run_layer1()
         self.run_layer2()
+        self.runs += 1
+
+    # ---- the decoder's row operands, made by layer 2's launch ----
+    def attach_decoder_rows(self, node_type: int, G: torch.Tensor, l: Optional[torch.Tensor]):
+        """Have layer 2's launch also store Q[r] = l ∘ ((E[r] ∘ l)·G) for every row of
+        embeddings[node_type] (dg_gcn_fused_tab_dec_f32), and return Q [rows, 32] — or None when
+        the plan cannot: anything but the one-GPU forward-only plan whose layer 2 is the 32 -> 32
+        wave-table launch (self.preproj), h2 != 32, G / l not float32 [32, 32] / [32] and 16-byte
+        aligned, DG_DEC_PREPROJECT=0, or another (G, l) attached already (one attachment a plan:
+        the same pointers get the same Q).  Q holds the rows of a run() after this call
+        (decoder_rows_valid), computed from G and l as they are when that run's launch executes.
+        Only layer 2's table and launch are rebuilt; release_decoder_rows undoes it."""
+        if not knob("DG_DEC_PREPROJECT", True):
+            return None
+        tab = getattr(self, "_l2_tab", None)
+        if not self.preproj or tab is None or self.h2 != 32 or node_type not in tab[4]:
+            return None
+        if (G.dtype != torch.float32 or tuple(G.shape) != (32, 32) or not G.is_contiguous() or G.data_ptr() % 16
+                or G.device != self.embeddings[node_type].device):
+            return None
+        if l is not None and (l.dtype != torch.float32 or tuple(l.shape) != (32,) or l.data_ptr() % 16
+                              or l.device != G.device):
+            return None
+        key = (node_type, G.data_ptr(), None if l is None else l.data_ptr())
+        if self._dec is not None:
+            if self._dec["key"] != key:
+                return None
+            self._dec["users"] += 1
+            return self._dec["Q"]
+        tgts, d_in, d, balance, fused_t, plain = tab
+        E = self.embeddings[node_type]
+        Q = torch.zeros((E.shape[0], 32), dtype=torch.float32, device=E.device)
+        launch = kernels.PreparedFusedTab(tgts, d_in, d, balance=balance,
+                                          dec=kernels.TabDecSpec(fused_t.index(node_type), G, l, Q))
+        self._swap_l2(plain, launch)
+        self._dec = {"key": key, "Q": Q, "G": G, "l": l, "launch": launch, "users": 1, "runs": self.runs}
+        return Q
+
+    def release_decoder_rows(self, Q: torch.Tensor) -> None:
+        """Undo attach_decoder_rows for one holder of Q; the last one restores the plain layer-2
+        launch (the same E bitwise)."""
+        if self._dec is None or self._dec["Q"] is not Q:
+            return
+        self._dec["users"] -= 1
+        if self._dec["users"] > 0:
+            return
+        self._swap_l2(self._dec["launch"], self._l2_tab[5])
+        # (kept alive with the plan: a graph captured while attached still replays that launch)
+        self._dec_retired.append(self._dec)
+        self._dec = None
+
+    def decoder_rows_valid(self, Q: torch.Tensor) -> bool:
+        """Whether Q (of attach_decoder_rows) holds the rows of this plan's last run: the plan has
+        run since the attachment."""
+        return self._dec is not None and self._dec["Q"] is Q and self.runs > self._dec["runs"]
+
+    def _swap_l2(self, old, new) -> None:
+        L = self._layer2.launches
+        L[L.index(old)] = new
+        self.launch_groups[id(new)] = self.launch_groups[id(old)]
 
     def phases(self) -> List[Tuple[str, Callable[[], None]]]:
         """The forward as alternating ("compute", fn) / ("exchange", fn) phases: the device
@@ -1272,6 +1343,8 @@ class ForwardPlan:
                     tot += 4 * pj.n_rels * (din * dout + pj.out.shape[1] * dout)
             if layer == 1:
                 tot += self._post_bytes(launch)
+            else:
+                tot += self._dec_bytes(launch)
         return tot
 
     @staticmethod
@@ -1282,6 +1355,15 @@ class ForwardPlan:
             K, din, dout = pj.w.shape
             tot += 4 * pj.n_rels * (din * dout + pj.out.shape[1] * dout)
         return tot
+
+    @staticmethod
+    def _dec_bytes(launch) -> int:
+        """G / l read once and Q rows written once by a layer-2 launch that makes the decoder's
+        row operands."""
+        dec = getattr(launch, "dec", None)
+        if dec is None:
+            return 0
+        return 4 * (dec.G.numel() + (dec.l.numel() if dec.l is not None else 0) + dec.out.numel())
 
     def layer_bytes(self, layer: int) -> int:
         """Algorithmic (compulsory) HBM bytes of one layer's SpMM launches: the CSR once
@@ -1313,6 +1395,9 @@ class ForwardPlan:
                         rows = pj.out.shape[1]
                         tot += 4 * pj.n_rels * (din * dout + rows * dout)
                 tot += self._post_bytes(f)
+        else:
+            for f in L.launches:
+                tot += self._dec_bytes(f)
         return tot
 
 

@@ -471,6 +471,42 @@ class TabProjSpec:
     slab: Optional[Sequence[int]] = None  # relation k -> slab (None: slab k)
 
 
+@dataclass
+class TabDecSpec:
+    """The decoder's row operands made by a 32 -> 32 PreparedFusedTab launch (layer 2): for every
+    row r of target `target`, out[r] = l ∘ ((E[r] ∘ l)·G), stored by the wave that finishes E[r]
+    (dg_gcn_fused_tab_dec_f32), so that a DEDICOM score is out[r]·E[c]."""
+
+    target: int                   # index into the launch's targets
+    G: torch.Tensor               # float32 [32, 32]
+    l: Optional[torch.Tensor]     # float32 [32], or None (all ones)
+    out: torch.Tensor             # float32 [n_rows, 32]
+
+
+DEC_ROLE_BIT = 29  # dg_tab_desc.role: the finishing wave also stores the decoder's row operand
+
+
+def _mark_dec_rows(desc: np.ndarray, plan, stride: int, target: int, n_rows: int, q_ptr: int) -> int:
+    """Flag the finishing waves of `target`'s rows in a wave table's descriptors: role bit 29 and
+    the Q row's address (q_ptr + 128 B · row) in pad[0..1].  plan: (target, first row, rows per
+    workgroup) per workgroup, in launch order; wave w < rows per workgroup of a workgroup
+    finishes row first + w, if the target has it.  Returns the number of rows flagged."""
+    done = 0
+    for b, (t, r0, rpb) in enumerate(plan):
+        if t != target:
+            continue
+        for w in range(rpb):
+            if r0 + w >= n_rows:
+                continue
+            i = b * stride + w
+            addr = q_ptr + (r0 + w) * 32 * 4
+            desc["role"][i] |= np.uint32(1 << DEC_ROLE_BIT)
+            desc["pad"][i, 0] = np.uint32(addr & 0xffffffff).astype(np.int32)
+            desc["pad"][i, 1] = np.uint32(addr >> 32).astype(np.int32)
+            done += 1
+    return done
+
+
 def _tab_geometry(waves_t: Sequence[int], balance: bool) -> Tuple[int, int, List[int]]:
     """(waves per workgroup, wave-slot stride, rows per workgroup of each target) of a wave-table
     fused launch whose target t has waves_t[t] relations a row."""
@@ -523,7 +559,9 @@ class PreparedFusedTab(PreparedFusedSeg):
     form).  projs (TabProjSpec, d_in = d_out = 64, no peer): the launch also makes layer 2's
     operands from the rows it finishes (dg_gcn_fused_tab_post_f32); seg_form() then still runs the
     plain seg launch, which writes the rows only.  share_proj: one wave projects every row of
-    its workgroup onto its relation (_proj_jobs).  peer = (PeerExchange, slot):
+    its workgroup onto its relation (_proj_jobs).  dec (TabDecSpec, d_in = d_out = 32): the launch
+    also stores the decoder's row operands of one target's rows (dg_gcn_fused_tab_dec_f32); the
+    rows themselves are bitwise the plain launch's.  peer = (PeerExchange, slot):
     the rows also go to every peer and the launch ends with the exchange
     (dg_gcn_fused_tab_peer_f32; PreparedFusedSeg's peer form, bitwise the same rows).
 
@@ -537,10 +575,23 @@ class PreparedFusedTab(PreparedFusedSeg):
     order — so only the fp32 summation order within a group differs from the per-relation form."""
 
     def __init__(self, targets, d_in: int, d_out: int, peer=None, balance: bool = False,
-                 projs: Sequence[TabProjSpec] = (), share_proj: bool = True):
+                 projs: Sequence[TabProjSpec] = (), share_proj: bool = True, dec: Optional[TabDecSpec] = None):
         super().__init__(targets, d_in, d_out, peer=peer)
         specs = self._keep[0]
         narrow = d_in == d_out == 32 and all(s.w is None for s in specs) and peer is None
+        self.dec = dec
+        if dec is not None:
+            _dev(dec.G, torch.float32, "G")
+            _dev(dec.out, torch.float32, "Q")
+            if dec.l is not None:
+                _dev(dec.l, torch.float32, "l")
+            if (not narrow or not 0 <= dec.target < len(targets) or tuple(dec.G.shape) != (32, 32)
+                    or tuple(dec.out.shape) != (targets[dec.target][1], 32) or not dec.out.is_contiguous()
+                    or not dec.G.is_contiguous() or (dec.l is not None and tuple(dec.l.shape) != (32,))
+                    or dec.G.data_ptr() % 16 or dec.out.data_ptr() % 16
+                    or (dec.l is not None and dec.l.data_ptr() % 16)):
+                raise ValueError("dg_gcn_fused_tab_dec_f32: a 32 -> 32 launch, G [32, 32], l [32] or None, "
+                                 "Q [target rows, 32], all 16-byte aligned")
         if not (_tab_shape(d_in, d_out, specs) or narrow):
             raise ValueError("dg_gcn_fused_tab_f32: d_in = d_out = 64, 64 -> 32 with weight stacks, or "
                              "d_in = d_out = 32 without an exchange")
@@ -627,9 +678,14 @@ class PreparedFusedTab(PreparedFusedSeg):
                     tb.desc["pad"][i, 1] = np.uint32(addr >> 32).astype(np.int32)
         if not plan and peer is not None:
             raise ValueError("dg_gcn_fused_tab_peer_f32: the exchange needs at least one row a rank")
+        if dec is not None:  # (pad[0..1]: the peer form's fields, free in the one-GPU 32 -> 32 form)
+            _mark_dec_rows(tb.desc, plan, stride, dec.target, targets[dec.target][1], dec.out.data_ptr())
         self._tab = tb.upload(self, len(plan), nw, stride, specs[0].x.device)
         self.n_blocks, self.nw = len(plan), nw
-        if self._xchg is not None:
+        if dec is not None:
+            self._keep = self._keep + (dec,)
+            self._tfn, self._tname = _lib.load().dg_gcn_fused_tab_dec_f32, "dg_gcn_fused_tab_dec_f32"
+        elif self._xchg is not None:
             self._tfn, self._tname = _lib.load().dg_gcn_fused_tab_peer_f32, "dg_gcn_fused_tab_peer_f32"
         elif self.projs:
             self._keep = self._keep + (self.projs,)
@@ -638,7 +694,11 @@ class PreparedFusedTab(PreparedFusedSeg):
             self._tfn, self._tname = _lib.load().dg_gcn_fused_tab_f32, "dg_gcn_fused_tab_f32"
 
     def __call__(self, stream=None) -> None:
-        if self._xchg is not None:
+        if self.dec is not None:
+            check(self._tfn(ctypes.byref(self._tab), self.d_in, self.d_out, self.dec.G.data_ptr(),
+                            self.dec.l.data_ptr() if self.dec.l is not None else None, _stream_ptr(stream)),
+                  self._tname)
+        elif self._xchg is not None:
             check(self._tfn(ctypes.byref(self._tab), self.d_in, self.d_out, self._xchg, _stream_ptr(stream)),
                   self._tname)
         else:
@@ -1634,14 +1694,53 @@ def upload_alias(degrees, device) -> torch.Tensor:
     return torch.from_numpy(alias_table(degrees).view(np.int32)).to(device)
 
 
+# Row producers: plans whose embedding tensors a decoder may ask for row operands
+# (ForwardPlan.attach_decoder_rows), found from the tensor a PreparedDecoderHinge is given.
+_ROW_PRODUCERS: dict = {}  # data_ptr -> (weakref to the plan, node type)
+
+
+def register_row_producer(tensor: torch.Tensor, plan, node_type) -> None:
+    """`tensor` is plan.embeddings[node_type]: a decoder built on it may attach to the plan."""
+    import weakref
+
+    for k in [k for k, (ref, _) in _ROW_PRODUCERS.items() if ref() is None]:
+        del _ROW_PRODUCERS[k]
+    _ROW_PRODUCERS[tensor.data_ptr()] = (weakref.ref(plan), node_type)
+
+
+def row_producer(tensor: torch.Tensor):
+    """(plan, node type) whose embedding table `tensor` is, or None."""
+    hit = _ROW_PRODUCERS.get(tensor.data_ptr())
+    if hit is None:
+        return None
+    plan, node_type = hit[0](), hit[1]
+    if plan is None or plan.embeddings.get(node_type) is None:
+        return None
+    e = plan.embeddings[node_type]
+    if e.data_ptr() != tensor.data_ptr() or e.shape != tensor.shape or e.stride() != tensor.stride():
+        return None
+    return plan, node_type
+
+
 class PreparedDecoderHinge:
     """dg_decoder_hinge_f32 on fixed buffers: sampled (or given) negatives, positive and
-    negative scores of n pairs and the hinge loss, in one launch."""
+    negative scores of n pairs and the hinge loss, in one launch.
+
+    preproject (None: the DG_DEC_PREPROJECT knob, default on): when row_table is the embedding
+    table of a ForwardPlan that accepts the attachment (ForwardPlan.attach_decoder_rows: a
+    one-GPU forward-only plan in the 32 -> 32 wave-table form) and the batch scores at least as
+    many pair sides as the table has rows (2n >= rows), the plan's layer-2 launch also stores
+    Q[r] = l ∘ ((E[r] ∘ l)·G) and this decoder scores by dot products
+    (dg_decoder_hinge_rows_f32).  Q is valid only once the plan has run since the attachment: a
+    call before that launches dg_decoder_hinge_f32 (`entry` names the entry point of the last
+    call).  Contract: an attached decoder scores with G and l as they were when the plan last
+    ran — they must not change between the plan's run and the decoder's call (in training, Adam
+    updates them after the decoder).  release() detaches."""
 
     def __init__(self, row_table: torch.Tensor, col_table: torch.Tensor, rows: torch.Tensor,
                  cols: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor], margin: float,
                  alias: Optional[torch.Tensor] = None, neg_rows: Optional[torch.Tensor] = None,
-                 seed: int = 0, offset: int = 0):
+                 seed: int = 0, offset: int = 0, preproject: Optional[bool] = None):
         for t, nm, dt in ((row_table, "row_table", torch.float32), (col_table, "col_table", torch.float32),
                           (rows, "rows", torch.int32), (cols, "cols", torch.int32), (G, "G", torch.float32)):
             _dev(t, dt, nm)
@@ -1666,7 +1765,7 @@ class PreparedDecoderHinge:
         self.neg = torch.empty(n, device=dev)
         self.neg_rows = torch.empty(n, device=dev, dtype=torch.int32)
         self.loss = torch.empty(1, device=dev)
-        self._ws = torch.zeros(4 + -(-n // 32), device=dev)  # ticket word + partials
+        self._ws = torch.zeros(4 + -(-n // 8), device=dev)  # ticket word + partials (either entry point)
         self._keep = (row_table, col_table, rows, cols, G, l, alias, neg_rows)
         self.seed, self.offset = seed, offset
         self._args = [row_table.data_ptr(), row_table.shape[1], col_table.data_ptr(), col_table.shape[1],
@@ -1676,11 +1775,52 @@ class PreparedDecoderHinge:
                       self.pos.data_ptr(), self.neg.data_ptr(), self.neg_rows.data_ptr(), self.loss.data_ptr(),
                       self._ws.data_ptr()]
         self._fn = _lib.load().dg_decoder_hinge_f32
+        self.entry = "dg_decoder_hinge_f32"  # the entry point of the last call
+        # row operands from the plan that makes row_table
+        self._plan = self.Q = None
+        if preproject is None:
+            preproject = knob("DG_DEC_PREPROJECT", True)
+        prod = row_producer(row_table) if preproject else None
+        if (prod is not None and d == 32 and 2 * n >= row_table.shape[0] and col_table.data_ptr() % 16 == 0
+                and col_table.is_contiguous()):
+            plan, node_type = prod
+            Q = plan.attach_decoder_rows(node_type, G, l)
+            if Q is not None:
+                self._plan, self.Q = plan, Q
+                self._rows_fn = _lib.load().dg_decoder_hinge_rows_f32
+                a = self._args
+                self._rows_args = [Q.data_ptr(), Q.shape[1]] + a[2:12] + [d] + a[15:]
+
+    @property
+    def attached(self) -> bool:
+        return self._plan is not None
+
+    def release(self) -> None:
+        """Detach from the plan (its layer 2 goes back to the plain launch); later calls score
+        with dg_decoder_hinge_f32."""
+        if self._plan is not None:
+            self._plan.release_decoder_rows(self.Q)
+            self._plan = self.Q = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
     def __call__(self, stream=None) -> None:
+        # Q holds the rows of the plan's last run only if it ran since the attachment (host-side
+        # check; under graph capture it sees the plan.run() captured before this call)
+        if self._plan is not None and self._plan.decoder_rows_valid(self.Q):
+            a = list(self._rows_args)
+            a[9], a[10] = self.seed & (2**64 - 1), self.offset & (2**64 - 1)
+            self.entry = "dg_decoder_hinge_rows_f32"
+            check(self._rows_fn(*a, _stream_ptr(stream)), self.entry)
+            return
         a = list(self._args)
         a[9], a[10] = self.seed & (2**64 - 1), self.offset & (2**64 - 1)
-        check(self._fn(*a, _stream_ptr(stream)), "dg_decoder_hinge_f32")
+        self.entry = "dg_decoder_hinge_f32"
+        check(self._fn(*a, _stream_ptr(stream)), self.entry)
 
 
 # --------------------------------------------------------------------------------------

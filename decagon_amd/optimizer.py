@@ -140,13 +140,15 @@ class DecagonOptimizer:
             negs = self._idx_dev(ctx, self.neg_samples, row_t.shape[0])
             if negs.numel() != rows.numel():
                 raise InvalidArgumentError("neg_samples must have one entry per batch edge")
-            op = kernels.PreparedDecoderHinge(row_t, col_t, rows, cols, G, l, self.margin, neg_rows=negs)
+            # (preproject=False: a decoder per call, built after the embeddings were evaluated)
+            op = kernels.PreparedDecoderHinge(row_t, col_t, rows, cols, G, l, self.margin, neg_rows=negs,
+                                              preproject=False)
         else:
             s = self._sampler(ctx)
             if s.tables[e].shape[0] > row_t.shape[0]:
                 raise InvalidArgumentError("degrees list longer than the row embedding table")
             op = kernels.PreparedDecoderHinge(row_t, col_t, rows, cols, G, l, self.margin, alias=s.tables[e],
-                                              seed=self.seed, offset=s.counter)
+                                              seed=self.seed, offset=s.counter, preproject=False)
             s.counter += rows.numel()
         op()
         return op.pos, op.neg, op.loss[0], op.neg_rows

@@ -253,9 +253,10 @@ int dg_gcn_fused_seg_f32(const dg_seg_group* groups /* HOST */, int32_t n_groups
  * wave per relation; a table that deals a group's pairs over several waves (PreparedFusedTab's
  * balance) re-associates the group's fp32 sum.  desc.role is not read by dg_gcn_fused_tab_f32 or
  * its peer form (the host builder still records the round-5 normalising role in bits 0-20 and 31);
- * dg_gcn_fused_tab_post_f32 reads bits 24-27 and 30, and dg_spmm_seg_tab_f32 bits 8-15, as described
+ * dg_gcn_fused_tab_post_f32 reads bits 24-27 and 30, dg_gcn_fused_tab_dec_f32 bit 29, and dg_spmm_seg_tab_f32 bits 8-15, as described
  * with them.  pad[0..1] belong to the peer form (below) or, in a projecting table, hold the P
- * row's address; pad[4] is unused.
+ * row's address, or, on a flagged finishing wave of dg_gcn_fused_tab_dec_f32's table, the Q row's;
+ * pad[4] is unused.
  * Shapes: d_in = d_out = 64; d_in = 64, d_out = 32 with W slabs (desc.w: the aggregate times the
  * relation's slab, so such a wave holds pairs of one relation); d_in = d_out = 32 (no exchange
  * form).  Replaces layers.py:85-94 / 109-118 and model.py:74-75, 85-88 as dg_gcn_fused_seg_f32
@@ -299,6 +300,17 @@ int dg_gcn_fused_tab_f32(const dg_wave_table* table /* HOST */, int32_t d_in, in
  * jobs, hence the separate entry point; arguments are checked as dg_gcn_fused_tab_f32's, and
  * only d_in = d_out = 64 is accepted. */
 int dg_gcn_fused_tab_post_f32(const dg_wave_table* table /* HOST */, int32_t d_in, int32_t d_out, void* stream);
+
+/* dg_gcn_fused_tab_f32 for a d_in = d_out = 32 table (layer 2 over pre-projected operands) that
+ * also makes the DEDICOM decoder's row operands: the finishing wave of a row whose desc.role has
+ * bit 29 set stores, after the row itself, Q[r] = l ∘ ((row ∘ l)·G) — 32 floats at the 16-byte
+ * aligned address in pad[0] (low half) and pad[1] (high half) — so that a score is the dot
+ * product Q[r]·E[c] (dg_decoder_hinge_rows_f32).  G is [32][32] row-major, l [32] or NULL (all
+ * ones), both device, 16-byte aligned (DG_EALIGN otherwise).  The summation order is fixed: Q is
+ * bitwise reproducible, and the rows are bitwise dg_gcn_fused_tab_f32's of the same table.  Other
+ * shapes, or G == NULL, give DG_EINVAL. */
+int dg_gcn_fused_tab_dec_f32(const dg_wave_table* table /* HOST */, int32_t d_in, int32_t d_out, const float* G,
+                             const float* l, void* stream);
 
 /* dg_gcn_fused_tab_f32 with the peer-store exchange (config S at N = 2 with --exchange peer):
  * every finished row also goes to every peer's copy of its target — desc.pad[0] = the row's
@@ -695,6 +707,22 @@ int dg_decoder_hinge_f32(const float* row_table, int64_t ld_row, const float* co
                          uint64_t seed, uint64_t offset, int32_t n, const float* G,
                          const float* l, int32_t d, float margin, float* pos, float* neg,
                          int32_t* neg_rows_out, float* loss, void* workspace, void* stream);
+
+/* dg_decoder_hinge_f32 over row operands (d = 32): Q[r] = l ∘ ((row_table[r] ∘ l)·G), [.., ld_q],
+ * as dg_gcn_fused_tab_dec_f32 stores them, takes the place of row_table, G and l, and
+ * score(r, c) = Q[r]·col_table[c].  Draws, outputs, the loss' hand-off and its reproducibility
+ * are dg_decoder_hinge_f32's, over blocks of DG_DEC_ROWS_PAIRS pairs: workspace is 16-byte
+ * aligned, 16 + 4*ceil(n/8) bytes, all zero before the first call.  Q and col_table are 16-byte
+ * aligned, ld_q and ld_col multiples of 4 (DG_EALIGN otherwise); d must be 32, n >= 1.  The scores
+ * are those of G and l at the time Q was made. */
+#ifndef DG_DEC_ROWS_PAIRS
+#define DG_DEC_ROWS_PAIRS 16
+#endif
+int dg_decoder_hinge_rows_f32(const float* Q, int64_t ld_q, const float* col_table, int64_t ld_col,
+                              const int32_t* rows, const int32_t* cols, const int32_t* neg_rows,
+                              const uint32_t* alias_table, int32_t range, uint64_t seed, uint64_t offset,
+                              int32_t n, int32_t d, float margin, float* pos, float* neg,
+                              int32_t* neg_rows_out, float* loss, void* workspace, void* stream);
 
 /* Hinge loss (T12):  loss[0] = sum_p relu(neg[p] - pos[p] + margin).
  * Replaces DecagonOptimizer._hinge_loss  optimizer.py:116-120.  Single workgroup,
