@@ -104,12 +104,6 @@ class DgSegGroup(ctypes.Structure):
     ]
 
 
-class DgTabDesc(ctypes.Structure):
-    """dg_tab_desc: one wave's 64-byte descriptor (the wave-table fused launch)."""
-    _fields_ = [("x", c_void_p), ("w", c_void_p), ("orow", c_void_p), ("cnt", c_int32), ("x_ld", c_int32),
-                ("ovf", c_int32), ("role", ctypes.c_uint32), ("wr", ctypes.c_uint32), ("pad", c_int32 * 5)]
-
-
 class DgWaveTable(ctypes.Structure):
     _fields_ = [("pairs", c_void_p), ("ovf", c_void_p), ("desc", c_void_p), ("n_blocks", c_int32),
                 ("nw", c_int32), ("nw_stride", c_int32), ("slot_pairs", c_int32)]

@@ -23,6 +23,7 @@
 //    slice 8(l>>3) .. +8), 32 fmaf, a butterfly over the 8 slices → z = y·W_k]
 // then the chunk's waves add their rows in relation order (LDS, one barrier) and the first
 // wave of the row writes out[c][r].  Fixed order, no atomics: bitwise reproducible.
+#include <cstddef>
 #include <vector>
 
 #include "common.h"
@@ -473,6 +474,22 @@ __global__ __launch_bounds__(64 * NW) void gcn_fused_seg_kernel(const FsArgs a) 
 // past the first 64 follow in batches of 64 from `ovf`.  Batches of 64 as in the seg form, so
 // the results are bitwise the seg form's.
 static_assert(sizeof(dg_tab_desc) == 64, "dg_tab_desc: one s_load_dwordx16");
+// (the host builder's dtype, decagon_amd/wavetable.py DESC, is compared with these offsets)
+static_assert(offsetof(dg_tab_desc, x) == 0, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, w) == 8, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, orow) == 16, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, cnt) == 24, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, x_ld) == 28, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, ovf) == 32, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, role) == 36, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, wr) == 40, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, aux_lo) == 44, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, aux_hi) == 48, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, gwaves) == 52, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, first_wave) == 56, "dg_tab_desc layout");
+static_assert(offsetof(dg_tab_desc, reserved) == 60, "dg_tab_desc layout");
+static_assert(kFsMaxRpb == DG_TAB_MAX_ROW_SLOTS && DG_TAB_ROLE_PROJ_SLOTS_BITS == DG_TAB_MAX_ROW_SLOTS,
+              "dg_tab_desc: one mask bit per row slot");
 // pairs: [blocks * NW * 64] first batch of each wave (hand-out order); desc: [blocks * NW];
 // ovf: later batches, 64 entries each.  (Separate pointer arguments: loaded together.)
 // A wave's relation sum from its wave-table slot (the first pairs already in `first`): batches
@@ -639,6 +656,12 @@ __device__ __forceinline__ uint32_t slot_lane_offset(int lane, int S) {
     return 8u * (uint32_t)((lane / LP) * q + (m < q ? m : q - 1));
 }
 
+// The 64-bit address a descriptor carries in its auxiliary words (a projection job's P row, a
+// flagged finishing wave's Q row).
+__device__ __forceinline__ float4* tab_aux_row(const dg_tab_desc& D) {
+    return reinterpret_cast<float4*>(((uint64_t)(uint32_t)D.aux_hi << 32) | (uint32_t)D.aux_lo);
+}
+
 // A float4 read as a global_load (the pointer is known to address device memory), not the flat
 // load a pointer out of a descriptor gets.
 __device__ __forceinline__ float4 load4_global(const float* p) {
@@ -648,15 +671,15 @@ __device__ __forceinline__ float4 load4_global(const float* p) {
 }
 
 // PEER (dg_gcn_fused_tab_peer_f32): each finished row also goes to every peer's copy of its
-// target (desc.pad[0] = the row's byte offset in the target, pad[1] = the target's bytes), and
+// target (desc.aux_lo = the row's byte offset in the target, aux_hi = the target's bytes), and
 // the launch ends with the exchange (peer.h).
 // LP = 8: the 32 -> 32 instance (plain sums over a 32-float operand, gcn_fused_seg_kernel<8, false>'s
 // rows bit for bit when every wave holds one relation).
 // POST (dg_gcn_fused_tab_post_f32; layer 1, 64 -> 64): the layer-2 operands P_k = H1·W2_k of the
 // workgroup's rows are made here, where the H1 rows are born.  The finishing wave also leaves its
 // row in LDS, one more barrier follows, and every wave whose descriptor carries a projection job
-// (role bit 30; its row slots in the mask of bits 24-27, W2_k in desc.w, the P row of row slot 0
-// in pad[0..1], slot s's row 128 bytes · s further) multiplies each of those rows by its W slab —
+// (DG_TAB_ROLE_PROJ_BIT; its row slots in the PROJ_SLOTS mask, W2_k in desc.w, the P row of row
+// slot 0 in the auxiliary words, slot s's row 128 bytes · s further) multiplies each of those rows by its W slab —
 // tab_wave<PROJ>'s lane mapping and arithmetic — and stores the 32 floats: one slice load serves
 // every row of the workgroup that the relation is sourced from.
 // A wave's eight W-slice loads are issued once its own gathers are done, before the first
@@ -670,7 +693,7 @@ __device__ __forceinline__ float4 load4_global(const float* p) {
 // DEC (dg_gcn_fused_tab_dec_f32; layer 2, 32 -> 32): the DEDICOM decoder's row operands
 // Q[r] = l ∘ ((E[r] ∘ l)·G) are made here, where the embedding row is born, so a score is the dot
 // product Q[r]·E[c] (decoder.hip, decoder_rows_hinge_kernel).  A finishing wave whose descriptor
-// carries role bit 29 (the Q row's address in pad[0..1]) passes the row it stored to all its lanes
+// carries DG_TAB_ROLE_DEC_BIT (the Q row's address in the auxiliary words) passes the row it stored to all its lanes
 // through its own ybuf slot and multiplies it by G: no second barrier, the other waves are done.
 template <bool PROJ, int NW, bool PEER, int LP = 16, bool POST = false, bool DEC = false>
 __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restrict__ pairs,
@@ -703,7 +726,7 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
     // the branch into a round trip of its own
     asm volatile("" ::"s"(D.x), "s"(D.w), "s"(D.orow), "s"(D.cnt), "s"(D.x_ld), "s"(D.ovf), "s"(D.role), "s"(D.wr),
                  "s"(ovf));
-    if constexpr (POST || DEC) asm volatile("" ::"s"(D.pad[0]), "s"(D.pad[1]));
+    if constexpr (POST || DEC) asm volatile("" ::"s"(D.aux_lo), "s"(D.aux_hi));
 #ifdef DG_FSEG_PROF
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #endif
@@ -715,7 +738,7 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
     // l & 7, and l at both — issued here as POST's W slice is, by the flagged finishing waves only
     // (48 VGPRs as the plain instance; issued before the gather loop instead: 66 VGPRs and the same
     // 4.27-4.33 µs a launch at config S)
-    const bool djob = DEC && ((D.role >> 29) & 1u) && D.orow != nullptr;  // wave-uniform
+    const bool djob = DEC && ((D.role >> DG_TAB_ROLE_DEC_BIT) & 1u) && D.orow != nullptr;  // wave-uniform
     float4 gv[DEC ? 4 : 1], lin, lout;  // (read only under djob)
     if constexpr (DEC) {
         lin = lout = make_float4(1.f, 1.f, 1.f, 1.f);
@@ -731,7 +754,7 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
     }
     // POST: this lane's slice of the job's W2_k (rows 8(l>>3) .. +8, output float4 l & 7), issued
     // now that the gathers are folded (res) and waited for only after the second barrier
-    const bool pjob = POST && ((D.role >> 30) & 1u);  // wave-uniform
+    const bool pjob = POST && ((D.role >> DG_TAB_ROLE_PROJ_BIT) & 1u);  // wave-uniform
     float4 wv[POST ? 8 : 1];  // (read only under pjob)
     if constexpr (POST) {
         if (pjob) {
@@ -754,18 +777,19 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
     // the sum, then the groups are added in order across the lane sets (lane set 0 reads set v
     // from lane ^ DOUT4·v), relu'd and stored.  The same adds, butterflies and order as the
     // per-group normalising waves of round 5 plus the nbuf hand-off: the same bits.
-    // desc.pad[2]: K − 1 of group u in bits 4u .. 4u+3; desc.pad[3]: the row slot's first wave.
+    // desc.gwaves: K − 1 of group u in bits 4u .. 4u+3; desc.first_wave: the row slot's first wave.
     if (D.orow != nullptr) {
         constexpr int SETS = 64 / DOUT4;
-        const int gc = D.wr & 0xff;
-        const uint32_t kc = (uint32_t)D.pad[2];
+        constexpr uint32_t kGw = (1u << DG_TAB_GWAVES_BITS) - 1u;
+        const int gc = D.wr & ((1u << DG_TAB_WR_GROUPS_BITS) - 1u);
+        const uint32_t kc = (uint32_t)D.gwaves;
         const int u = lane / DOUT4, q = lane % DOUT4;
-        int gb = D.pad[3];
+        int gb = D.first_wave;
 #pragma unroll
         for (int v = 0; v + 1 < SETS; ++v)
-            if (v < u && v < gc) gb += (int)((kc >> (4 * v)) & 15u) + 1;
+            if (v < u && v < gc) gb += (int)((kc >> (DG_TAB_GWAVES_BITS * v)) & kGw) + 1;
         const bool mine = u < gc;
-        const int K = mine ? (int)((kc >> (4 * u)) & 15u) + 1 : 1;
+        const int K = mine ? (int)((kc >> (DG_TAB_GWAVES_BITS * u)) & kGw) + 1 : 1;
         const float4 sum = lds_ordered_sum<DOUT4>(&zbuf[mine ? gb : 0], K, q);
         // tf.nn.l2_normalize: x * rsqrt(max(sum(x^2), 1e-12))
         float ss = sum.x * sum.x + sum.y * sum.y + sum.z * sum.z + sum.w * sum.w;
@@ -776,18 +800,18 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
         add_lane_sets<DOUT4, 1, SETS>(tot, nv, gc);  // ((n0 + n1) + n2) + ...
         DG_FS_STAMP(5);  // groups normalised and summed
         if (lane < DOUT4) {
-            if ((D.wr >> 8) & 1) {
+            if ((D.wr >> DG_TAB_WR_RELU_BIT) & 1) {
                 tot.x = fmaxf(tot.x, 0.f);
                 tot.y = fmaxf(tot.y, 0.f);
                 tot.z = fmaxf(tot.z, 0.f);
                 tot.w = fmaxf(tot.w, 0.f);
             }
             reinterpret_cast<float4*>(D.orow)[lane] = tot;
-            if constexpr (POST) hbuf[(D.wr >> 16) & (kFsMaxRpb - 1)][lane] = tot;  // the row as stored
+            if constexpr (POST) hbuf[(D.wr >> DG_TAB_WR_SLOT_SHIFT) & (kFsMaxRpb - 1)][lane] = tot;  // (as stored)
             if constexpr (DEC) ybuf[wave][lane] = tot;  // (this wave's own slot: unused by plain sums)
             if constexpr (PEER)
-                dg::peer_store4(P, reinterpret_cast<const float*>(reinterpret_cast<const char*>(D.orow) - D.pad[0]),
-                                (uint32_t)D.pad[1], (uint32_t)D.pad[0] + 16u * lane, tot);
+                dg::peer_store4(P, reinterpret_cast<const float*>(reinterpret_cast<const char*>(D.orow) - D.aux_lo),
+                                (uint32_t)D.aux_hi, (uint32_t)D.aux_lo + 16u * lane, tot);
         }
         if constexpr (DEC) {
             // Q = l ∘ ((e ∘ l)·G) of the row just stored: lane (s, c) = (l >> 3, l & 7) multiplies
@@ -804,7 +828,7 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
                 dg::fma4(z, e.w * lin.w, gv[3]);
                 z = dg::xor_sum4_from<8>(z);
                 if (lane < 8) {
-                    float4* qrow = reinterpret_cast<float4*>(((uint64_t)(uint32_t)D.pad[1] << 32) | (uint32_t)D.pad[0]);
+                    float4* qrow = tab_aux_row(D);
                     qrow[lane] = make_float4(z.x * lout.x, z.y * lout.y, z.z * lout.z, z.w * lout.w);
                 }
             }
@@ -815,8 +839,9 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
         if (pjob) {
             // z = h·W2_k, tab_wave<PROJ>'s arithmetic: 32 fmaf over this lane's 8-row slice, then
             // the butterfly over the 8 slices; lanes 0-7 hold the 32 floats of the P row
-            float4* prow = reinterpret_cast<float4*>(((uint64_t)(uint32_t)D.pad[1] << 32) | (uint32_t)D.pad[0]);
-            const uint32_t slots = (D.role >> 24) & ((1u << kFsMaxRpb) - 1u);
+            float4* prow = tab_aux_row(D);
+            const uint32_t slots =
+                (D.role >> DG_TAB_ROLE_PROJ_SLOTS_SHIFT) & ((1u << DG_TAB_ROLE_PROJ_SLOTS_BITS) - 1u);
 #pragma unroll
             for (int sl = 0; sl < kFsMaxRpb; ++sl) {
                 if (!((slots >> sl) & 1u)) continue;  // wave-uniform
@@ -852,7 +877,7 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
 // (XCD-contiguous item map included), waves, batches and sums — bitwise its chunk partials —
 // with each wave's segment, gather base, W slab and (for the first wave of a row's chunk) the
 // partial row it writes and the waves it sums precomputed on the host: desc.orow != NULL marks
-// that wave, desc.role bits 8-15 the chunk's waves.
+// that wave, desc.role's SEG_WAVES field the chunk's waves.
 template <bool PROJ, int NW>
 __global__ __launch_bounds__(64 * NW) void seg_tab_kernel(const uint2* __restrict__ pairs,
                                                           const dg_tab_desc* __restrict__ desc,
@@ -872,7 +897,7 @@ __global__ __launch_bounds__(64 * NW) void seg_tab_kernel(const uint2* __restric
     if (lane < DOUT4) zbuf[wave][lane] = res;  // relations past the group's end add zeros
     __syncthreads();
     if (D.orow != nullptr && lane < DOUT4) {
-        const int K = (D.role >> 8) & 0xff;
+        const int K = (D.role >> DG_TAB_ROLE_SEG_WAVES_SHIFT) & ((1u << DG_TAB_ROLE_SEG_WAVES_BITS) - 1u);
         reinterpret_cast<float4*>(D.orow)[lane] = lds_ordered_sum<DOUT4>(&zbuf[wave], K, lane);
     }
 }

@@ -28,7 +28,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import kernels
+from . import kernels, wavetable
 from ._lib import DG_EPI_L2NORM, DG_EPI_RELU, DG_MAX_GROUPS
 from .sparse import HostCSR, MergedCSR, chunk_segments, merge_chunks, merge_windows, staged_layout
 from .tuning import knob
@@ -853,7 +853,7 @@ class ForwardPlan:
         rels = {et: self.g.groups[et].n_rels for et in self.edge_types}
         waves_t = [sum(rels[et] for et in self.targets[i]) for i in order]
         sourced_t = [sum(k for et, k in rels.items() if et[1] == i) for i in order]
-        return kernels.tab_proj_fit(waves_t, sourced_t, _tab_balance(self.h1, self.h1), L2_PREPROJECT_SHARE)
+        return wavetable.tab_proj_fit(waves_t, sourced_t, _tab_balance(self.h1, self.h1), L2_PREPROJECT_SHARE)
 
     def _spec(self, et, x: torch.Tensor, out, d) -> kernels.RelGroupSpec:
         grp = self.g.groups[et]
@@ -1037,7 +1037,7 @@ class ForwardPlan:
             d_in = self.h1 if seg_w else d
             for s in range(0, len(segs), DG_MAX_GROUPS):
                 part = segs[s:s + DG_MAX_GROUPS]
-                if WAVE_TABLE and kernels._tab_shape(d_in, d, part):
+                if WAVE_TABLE and wavetable._tab_shape(d_in, d, part):
                     launches.append(kernels.PreparedSegTab(part, d_in, d))  # (the wave-table form)
                 else:
                     launches.append(kernels.PreparedSeg(part, d_in, d))

@@ -12,15 +12,17 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, wavetable
 from .tuning import knob
 from ._lib import (DgAdamSeg, DgEpiGroup, DgFusedTarget, DgGemmDesc, DgL2gGroup, DgProj, DgRelGroup,
                    DgStagedGroup, DgStagedProj, check)
+# the table helpers that callers found here before wavetable.py existed
+from .wavetable import _balanced_waves, _proj_jobs, _tab_geometry, tab_proj_fit  # noqa: F401
 
 
 def _stream_ptr(stream: Optional[torch.cuda.Stream] = None) -> int:
@@ -332,129 +334,29 @@ class PreparedFusedSeg:
               "dg_gcn_fused_seg_f32")
 
 
-class _WaveTable:
-    """Host builder of a dg_wave_table (decagon_hip.h): per wave slot a 64-byte descriptor and
-    the first S pairs of its segment (in the hand-out order of its gather form: pair m in lane
-    16·(m & 3) + (m >> 2), stored compactly at (m & 3)·S/4 + (m >> 2); with 32-float rows, lp = 8,
-    eight pairs are handed out at once: lane 8·(m & 7) + (m >> 3), stored at (m & 7)·S/8 + (m >> 3)),
-    the rest in batches of 64 in an overflow array.  S (slot_pairs, round 6) is the smallest of 16 / 32 / 48 / 64
-    holding the first batch of ≥ SLOT_COVER of the non-empty waves: a wave then fetches S·8 B
-    where round 5 fetched 512 B whatever its length (a config-S wave holds 7–81 pairs)."""
-
-    SLOT_COVER = 0.97
-
-    DESC = np.dtype([("x", "<u8"), ("w", "<u8"), ("orow", "<u8"), ("cnt", "<i4"), ("x_ld", "<i4"), ("ovf", "<i4"),
-                     ("role", "<u4"), ("wr", "<u4"), ("pad", "<i4", 5)])
-
-    def __init__(self, specs: Sequence[SegSpec], n_slots: int, proj: bool, lp: int = 16):
-        assert self.DESC.itemsize == 64 and lp in (8, 16) and not (proj and lp == 8)
-        self.specs, self.proj = list(specs), proj
-        self.G = 64 // lp  # pairs handed out at once
-        self.host = [(s.rowptr.cpu().numpy(), s.seg.cpu().numpy(), s.vcol.cpu().numpy(), s.val.cpu().numpy(),
-                      None if s.slab is None else s.slab.cpu().numpy()) for s in specs]
-        self.n_slots = n_slots
-        self.pv: dict = {}  # wave slot -> its pairs [cnt, 2] (laid out at upload, once S is known)
-        self.desc = np.zeros(n_slots, self.DESC)
-        # entry of pair m within a batch: its lane in the DPP hand-out (both layers since round 6)
-        m = np.arange(64)
-        self.lane_of = (64 // self.G) * (m % self.G) + m // self.G
-
-    def bounds(self, g: int, k: int, r: int) -> Tuple[int, int]:
-        """[beg, end) of relation k's segment (of spec g) in row r."""
-        s = self.specs[g]
-        rowptr, seg = self.host[g][:2]
-        c, t = divmod(k, s.chunk)
-        si = (c * s.n_rows + r) * s.chunk + t
-        beg = int(seg[si])
-        end = int(seg[si + 1]) if t + 1 < s.chunk else int(rowptr[c * s.n_rows + r + 1])
-        return beg, end
-
-    def seg_len(self, g: int, k: int, r: int) -> int:
-        beg, end = self.bounds(g, k, r)
-        return end - beg
-
-    def relation(self, i: int, g: int, k: int, r: int) -> None:
-        """Wave slot i gathers relation k (of spec g) of row r."""
-        beg, end = self.bounds(g, k, r)
-        self.wave(i, g, r, [(k, 0, end - beg)])
-
-    def wave(self, i: int, g: int, r: int, pieces) -> None:
-        """Wave slot i gathers the pieces [(k, a, b)] of row r, in order: pairs a..b of relation
-        k's segment (of spec g) — with a weight stack (layer 2 reassociated) one relation's only,
-        since the wave multiplies its aggregate by that relation's W slab."""
-        s = self.specs[g]
-        vcol, val, slab = self.host[g][2:]
-        d = self.desc
-        vcs, vvs = [], []
-        for k, a, b in pieces:
-            beg, _ = self.bounds(g, k, r)
-            vc = vcol[beg + a:beg + b].astype(np.int64)
-            if self.proj:
-                sl = int(slab[k]) if slab is not None else k
-                vc = vc - sl * s.n_cols  # plain rows of H
-                d["w"][i] = s.w.data_ptr() + sl * 64 * 32 * 4
-            vcs.append(vc)
-            vvs.append(val[beg + a:beg + b])
-        if self.proj and len({k for k, _, _ in pieces}) > 1:
-            raise ValueError("a reassociated wave gathers one relation")
-        vc = np.concatenate(vcs) if vcs else np.zeros(0, np.int64)
-        vv = np.concatenate(vvs) if vvs else np.zeros(0, np.float32)
-        cnt = len(vc)
-        d["x"][i], d["x_ld"][i], d["cnt"][i] = s.x.data_ptr(), s.x_ld, cnt
-        self.pv[i] = np.stack([vc.astype(np.int32), vv.astype(np.float32).view(np.int32)], 1)
-
-    def slot_pairs(self) -> int:
-        fixed = knob("DG_TAB_SLOT", 0)  # (A/B: a fixed slot size; 0 = by SLOT_COVER)
-        if fixed:
-            if fixed not in (16, 32, 48, 64):
-                raise ValueError("DG_TAB_SLOT: 16, 32, 48 or 64")
-            return fixed
-        cnts = np.array([len(p) for p in self.pv.values() if len(p)], np.int64)
-        if not len(cnts):
-            return 16
-        need = float(np.quantile(cnts, self.SLOT_COVER))
-        return next(S for S in (16, 32, 48, 64) if S >= need or S == 64)
-
-    def layout(self, S: int):
-        """(pairs [n_slots·S, 2], ovf [.., 2]) for first-batch slots of S pairs; sets desc.ovf."""
-        pairs = np.zeros((self.n_slots * S, 2), np.int32)
-        ovf: List[np.ndarray] = []
-        n_ovf = 0
-        m = np.arange(S)
-        compact = (m % self.G) * (S // self.G) + m // self.G  # slot entry of pair m (its lane's row-major rank)
-        for i, pv in self.pv.items():
-            cnt = len(pv)
-            m0 = min(cnt, S)
-            pairs[i * S + compact[:m0]] = pv[:m0]
-            if cnt > S:
-                self.desc["ovf"][i] = n_ovf
-                for q0 in range(S, cnt, 64):
-                    blk = np.zeros((64, 2), np.int32)
-                    n = min(64, cnt - q0)
-                    blk[self.lane_of[:n]] = pv[q0:q0 + n]
-                    ovf.append(blk)
-                    n_ovf += 64
-        return pairs, (np.concatenate(ovf) if ovf else np.zeros((64, 2), np.int32))
-
-    def upload(self, owner, n_blocks: int, nw: int, stride: int, dev) -> "_lib.DgWaveTable":
-        S = self.slot_pairs()
-        pairs, ovf = self.layout(S)
-        owner._pairs = torch.from_numpy(pairs).to(dev)
-        owner._ovf = torch.from_numpy(ovf).to(dev)
-        owner.slot_pairs = S
-        raw = torch.from_numpy(self.desc.view(np.uint8).copy())
-        owner._desc = torch.empty(raw.numel() + 64, dtype=torch.uint8, device=dev)
-        off = (-owner._desc.data_ptr()) % 64  # 64-byte aligned descriptors
-        owner._desc_v = owner._desc[off:off + raw.numel()]
-        owner._desc_v.copy_(raw.to(dev))
-        tab = _lib.DgWaveTable()
-        tab.pairs, tab.ovf, tab.desc = owner._pairs.data_ptr(), owner._ovf.data_ptr(), owner._desc_v.data_ptr()
-        tab.n_blocks, tab.nw, tab.nw_stride, tab.slot_pairs = n_blocks, nw, stride, S
-        return tab
+def _seg_data(s: SegSpec) -> wavetable.SegData:
+    """A validated SegSpec as the host table builder takes it: host arrays, integer addresses."""
+    return wavetable.SegData(s.rowptr.cpu().numpy(), s.seg.cpu().numpy(), s.vcol.cpu().numpy(), s.val.cpu().numpy(),
+                             None if s.slab is None else s.slab.cpu().numpy(), s.x.data_ptr(),
+                             None if s.w is None else s.w.data_ptr(), None if s.out is None else s.out.data_ptr(),
+                             s.x_ld, s.n_rows, s.n_cols, s.chunk, s.n_chunks, s.n_rels)
 
 
-def _tab_shape(d_in: int, d_out: int, specs) -> bool:
-    return d_in == 64 and (d_out == 64 or (d_out == 32 and all(s.w is not None for s in specs)))
+def _upload_table(owner, tab: wavetable.HostTable, dev) -> "_lib.DgWaveTable":
+    """A host-built wave table on the device (descriptors 64-byte aligned), its tensors and
+    counts kept on `owner`; returns the launch's dg_wave_table."""
+    owner._pairs = torch.from_numpy(tab.pairs).to(dev)
+    owner._ovf = torch.from_numpy(tab.ovf).to(dev)
+    owner.n_blocks, owner.nw, owner.slot_pairs = tab.n_blocks, tab.nw, tab.slot_pairs
+    raw = torch.from_numpy(tab.desc.view(np.uint8).copy())
+    owner._desc = torch.empty(raw.numel() + 64, dtype=torch.uint8, device=dev)
+    off = (-owner._desc.data_ptr()) % 64
+    owner._desc_v = owner._desc[off:off + raw.numel()]
+    owner._desc_v.copy_(raw.to(dev))
+    t = _lib.DgWaveTable()
+    t.pairs, t.ovf, t.desc = owner._pairs.data_ptr(), owner._ovf.data_ptr(), owner._desc_v.data_ptr()
+    t.n_blocks, t.nw, t.nw_stride, t.slot_pairs = tab.n_blocks, tab.nw, tab.stride, tab.slot_pairs
+    return t
 
 
 @dataclass
@@ -483,83 +385,16 @@ class TabDecSpec:
     out: torch.Tensor             # float32 [n_rows, 32]
 
 
-DEC_ROLE_BIT = 29  # dg_tab_desc.role: the finishing wave also stores the decoder's row operand
-
-
-def _mark_dec_rows(desc: np.ndarray, plan, stride: int, target: int, n_rows: int, q_ptr: int) -> int:
-    """Flag the finishing waves of `target`'s rows in a wave table's descriptors: role bit 29 and
-    the Q row's address (q_ptr + 128 B · row) in pad[0..1].  plan: (target, first row, rows per
-    workgroup) per workgroup, in launch order; wave w < rows per workgroup of a workgroup
-    finishes row first + w, if the target has it.  Returns the number of rows flagged."""
-    done = 0
-    for b, (t, r0, rpb) in enumerate(plan):
-        if t != target:
-            continue
-        for w in range(rpb):
-            if r0 + w >= n_rows:
-                continue
-            i = b * stride + w
-            addr = q_ptr + (r0 + w) * 32 * 4
-            desc["role"][i] |= np.uint32(1 << DEC_ROLE_BIT)
-            desc["pad"][i, 0] = np.uint32(addr & 0xffffffff).astype(np.int32)
-            desc["pad"][i, 1] = np.uint32(addr >> 32).astype(np.int32)
-            done += 1
-    return done
-
-
-def _tab_geometry(waves_t: Sequence[int], balance: bool) -> Tuple[int, int, List[int]]:
-    """(waves per workgroup, wave-slot stride, rows per workgroup of each target) of a wave-table
-    fused launch whose target t has waves_t[t] relations a row."""
-    nw = max([1] + list(waves_t))
-    stride = 8 if nw <= 8 else 16
-    if balance:
-        nw = stride  # every wave slot of a workgroup takes a share of its rows' pairs
-    return nw, stride, [min(nw // max(1, w), 4) for w in waves_t]
-
-
-def _proj_jobs(rows_present: Sequence[bool], n_rels: int, nw: int, share: bool = False):
-    """Projection jobs of one workgroup: per wave slot (nw of them) its job (row slots, relation)
-    or None.  The workgroup holds len(rows_present) row slots, each projected onto n_rels
-    relations; a slot without a row (the last workgroup of an odd row count) projects nothing.
-    Every (row, relation) goes to exactly one wave, and a wave holds one relation (one W slice).
-    Without `share` a wave takes one row, so no wave takes two (row, relation) jobs; with it, one
-    wave projects every present row onto its relation, so the relation's W slab is read once a
-    workgroup, not once a row.  The waves that do not finish a row (slots rpb .. nw-1: idle while
-    the finishing waves 0 .. rpb-1 work) are filled first.  None when the jobs of a full workgroup
-    (rows per workgroup × relations; with `share`, the relations) exceed nw: the form is not built."""
-    rpb = len(rows_present)
-    if (n_rels if share else rpb * n_rels) > nw:
-        return None
-    jobs: List[Optional[Tuple[Tuple[int, ...], int]]] = [None] * nw
-    order = list(range(rpb, nw)) + list(range(min(rpb, nw)))
-    present = tuple(slot for slot in range(rpb) if rows_present[slot])
-    if share:
-        todo = [(present, k) for k in range(n_rels)] if present else []
-    else:
-        todo = [((slot,), k) for slot in present for k in range(n_rels)]
-    for w, job in zip(order, todo):
-        jobs[w] = job
-    return jobs
-
-
-def tab_proj_fit(waves_t: Sequence[int], sourced_t: Sequence[int], balance: bool, share: bool = False) -> bool:
-    """Whether a wave-table launch whose target t has waves_t[t] relations a row has a wave slot
-    for every projection job: rows per workgroup × sourced_t[t] relations projected per row (with
-    `share`: sourced_t[t] jobs a workgroup)."""
-    nw, _, rpbs = _tab_geometry(waves_t, balance)
-    return all(_proj_jobs([True] * rpb, k, nw, share) is not None for rpb, k in zip(rpbs, sourced_t))
-
-
 class PreparedFusedTab(PreparedFusedSeg):
     """The same launch as PreparedFusedSeg (same targets, rows, waves and arithmetic: bitwise the
     same rows) through dg_gcn_fused_tab_f32: the wave table — each wave's 64-byte descriptor and
-    its segment's first 64 pairs at a fixed slot — is built here once, on the host, from the
-    chunk-merged CSR and segment starts of the specs (decagon_hip.h documents the layout).
+    its segment's first pairs at a fixed slot — is built once, on the host, from the chunk-merged
+    CSR and segment starts of the specs (wavetable.fused_table; decagon_hip.h documents the layout).
     Shapes: d_in = d_out = 64, 64 -> 32 with weight stacks, or d_in = d_out = 32 (one GPU: no peer
     form).  projs (TabProjSpec, d_in = d_out = 64, no peer): the launch also makes layer 2's
     operands from the rows it finishes (dg_gcn_fused_tab_post_f32); seg_form() then still runs the
     plain seg launch, which writes the rows only.  share_proj: one wave projects every row of
-    its workgroup onto its relation (_proj_jobs).  dec (TabDecSpec, d_in = d_out = 32): the launch
+    its workgroup onto its relation (wavetable._proj_jobs).  dec (TabDecSpec, d_in = d_out = 32): the launch
     also stores the decoder's row operands of one target's rows (dg_gcn_fused_tab_dec_f32); the
     rows themselves are bitwise the plain launch's.  peer = (PeerExchange, slot):
     the rows also go to every peer and the launch ends with the exchange
@@ -592,10 +427,9 @@ class PreparedFusedTab(PreparedFusedSeg):
                     or (dec.l is not None and dec.l.data_ptr() % 16)):
                 raise ValueError("dg_gcn_fused_tab_dec_f32: a 32 -> 32 launch, G [32, 32], l [32] or None, "
                                  "Q [target rows, 32], all 16-byte aligned")
-        if not (_tab_shape(d_in, d_out, specs) or narrow):
+        if not (wavetable._tab_shape(d_in, d_out, specs) or narrow):
             raise ValueError("dg_gcn_fused_tab_f32: d_in = d_out = 64, 64 -> 32 with weight stacks, or "
                              "d_in = d_out = 32 without an exchange")
-        proj = d_out != d_in
         if any(len(gs) > 64 // (d_out // 4) for _, _, gs, _ in targets):
             raise ValueError("dg_gcn_fused_tab_f32: at most 64 / (d_out / 4) groups a target (one lane set each)")
         self.projs = list(projs)
@@ -609,79 +443,15 @@ class PreparedFusedTab(PreparedFusedSeg):
             if (tuple(pj.w.shape[1:]) != (64, 32) or tuple(pj.out.shape) != (K, rows, 32) or len(slabs) != pj.n_rels
                     or any(not 0 <= x < K for x in slabs) or pj.out.data_ptr() % 16 or pj.w.data_ptr() % 16):
                 raise ValueError("projection jobs: w [K, 64, 32], P [K, target rows, 32], slabs inside both")
-        waves_t = [sum(s.n_rels for s in gs) for _, _, gs, _ in targets]
-        nw, stride, rpbs = _tab_geometry(waves_t, balance)
         self.balance = balance
-        plan = []  # (target, first row, rows per workgroup) per workgroup, in launch order
-        for t, (_, n_rows, _, _) in enumerate(targets):
-            rpb = rpbs[t]
-            plan += [(t, r0, rpb) for r0 in range(0, n_rows, rpb)]
-        tb = _WaveTable(specs, len(plan) * stride, proj, lp=d_in // 4)
-        g_first = np.cumsum([0] + [len(gs) for _, _, gs, _ in targets])
-        for b, (t, r0, rpb) in enumerate(plan):
-            out, n_rows, gspecs, relu = targets[t]
-            gc = len(gspecs)
-            nr = [s.n_rels for s in gspecs]
-            per_row = nw // rpb if balance else waves_t[t]  # wave slots of one row
-            counts = [[1] * gc for _ in range(rpb)]  # waves per group, per row slot
-            for slot in range(rpb):
-                r = r0 + slot
-                if r >= n_rows:
-                    continue
-                gs = [int(g_first[t]) + gl for gl in range(gc)]
-                if balance:
-                    waves = _balanced_waves(tb, gs, nr, r, per_row, proj)
-                else:  # one wave per relation, groups in order
-                    waves = [[[(k, 0, None)] for k in range(nr[gl])] for gl in range(gc)]
-                counts[slot] = [len(wg) for wg in waves]
-                w = slot * per_row
-                for gl, wg in enumerate(waves):
-                    for pieces in wg:
-                        tb.wave(b * stride + w, gs[gl], r,
-                                [(k, a, e if e is not None else tb.seg_len(gs[gl], k, r)) for k, a, e in pieces])
-                        w += 1
-            for w in range(nw):
-                i = b * stride + w
-                if w < rpb * gc:
-                    s2, gg = divmod(w, gc)
-                    gb = s2 * per_row + sum(counts[s2][:gg])
-                    tb.desc["role"][i] = ((1 << 31) | ((s2 * DG_MAX_GROUPS_TAB + gg) << 16) | (counts[s2][gg] << 8)
-                                          | gb)
-                if w < rpb and r0 + w < n_rows:
-                    tb.desc["orow"][i] = out.data_ptr() + (r0 + w) * d_out * 4
-                    tb.desc["wr"][i] = gc | ((1 if relu else 0) << 8) | (w << 16)
-                    tb.desc["pad"][i, 0] = (r0 + w) * d_out * 4  # (the peer form: row offset,
-                    tb.desc["pad"][i, 1] = n_rows * d_out * 4     # target bytes)
-                    # the row's finishing wave (round 6): each group's wave count − 1 in 4 bits,
-                    # and the row slot's first wave
-                    tb.desc["pad"][i, 2] = np.int32(np.uint32(sum((c - 1) << (4 * u)
-                                                                  for u, c in enumerate(counts[w]))))
-                    tb.desc["pad"][i, 3] = w * per_row
-            # projection jobs (role bit 30, the job's row slots in bits 24-27): W2_k in `w`, the
-            # address of row slot 0's P row in pad[0..1] (the peer form's fields: a projecting
-            # launch has no exchange)
-            rels = [(pj, k) for pj in self.projs if pj.target == t for k in range(pj.n_rels)]
-            if rels:
-                jobs = _proj_jobs([r0 + slot < n_rows for slot in range(rpb)], len(rels), nw, share_proj)
-                if jobs is None:
-                    raise ValueError(f"{rpb} rows x {len(rels)} projection jobs for {nw} wave slots")
-                for w, job in enumerate(jobs):
-                    if job is None:
-                        continue
-                    slots, (pj, k) = job[0], rels[job[1]]
-                    sl = k if pj.slab is None else int(pj.slab[k])
-                    i = b * stride + w
-                    addr = pj.out.data_ptr() + (sl * n_rows + r0) * 32 * 4
-                    tb.desc["role"][i] |= np.uint32((1 << 30) | (sum(1 << x for x in slots) << 24))
-                    tb.desc["w"][i] = pj.w.data_ptr() + sl * 64 * 32 * 4
-                    tb.desc["pad"][i, 0] = np.uint32(addr & 0xffffffff).astype(np.int32)
-                    tb.desc["pad"][i, 1] = np.uint32(addr >> 32).astype(np.int32)
-        if not plan and peer is not None:
-            raise ValueError("dg_gcn_fused_tab_peer_f32: the exchange needs at least one row a rank")
-        if dec is not None:  # (pad[0..1]: the peer form's fields, free in the one-GPU 32 -> 32 form)
-            _mark_dec_rows(tb.desc, plan, stride, dec.target, targets[dec.target][1], dec.out.data_ptr())
-        self._tab = tb.upload(self, len(plan), nw, stride, specs[0].x.device)
-        self.n_blocks, self.nw = len(plan), nw
+        data = {id(s): _seg_data(s) for s in specs}
+        self._tab = _upload_table(self, wavetable.fused_table(
+            [(out.data_ptr(), n_rows, [data[id(s)] for s in gs], relu) for out, n_rows, gs, relu in targets],
+            d_in, d_out, balance=balance,
+            projs=[wavetable.ProjData(pj.target, pj.w.data_ptr(), pj.out.data_ptr(), pj.n_rels, pj.slab)
+                   for pj in self.projs],
+            share_proj=share_proj, dec=None if dec is None else wavetable.DecData(dec.target, dec.out.data_ptr()),
+            peer=peer is not None, slot=knob("DG_TAB_SLOT", 0)), specs[0].x.device)
         if dec is not None:
             self._keep = self._keep + (dec,)
             self._tfn, self._tname = _lib.load().dg_gcn_fused_tab_dec_f32, "dg_gcn_fused_tab_dec_f32"
@@ -709,97 +479,17 @@ class PreparedFusedTab(PreparedFusedSeg):
         PreparedFusedSeg.__call__(self, stream)
 
 
-def _split_even(n: int, parts: int) -> List[Tuple[int, int]]:
-    """[a, b) slices of n items over `parts` waves, the first n % parts one longer."""
-    q, rem = divmod(n, parts)
-    out, a = [], 0
-    for p in range(parts):
-        e = a + q + (1 if p < rem else 0)
-        out.append((a, e))
-        a = e
-    return out
-
-
-def _balanced_waves(tb: "_WaveTable", gs, nr, r: int, slots: int, proj: bool):
-    """Row r's waves for PreparedFusedTab(balance=True): per group, a list of waves, each a list
-    of pieces (relation k, first pair, end pair) of the relation's segment.  `slots` wave slots
-    in all, at least one per group (per relation with weight stacks); the spare slots go, one at
-    a time, to the job whose share per wave is the largest (ties: the first)."""
-    if proj:  # jobs are relations: a reassociated wave multiplies by one relation's W slab
-        jobs = [(gl, k) for gl in range(len(gs)) for k in range(nr[gl])]
-        sizes = [tb.seg_len(gs[gl], k, r) for gl, k in jobs]
-    else:  # jobs are groups: every pair of a group gathers one row of the stacked operand
-        jobs = [(gl, None) for gl in range(len(gs))]
-        sizes = [sum(tb.seg_len(gs[gl], k, r) for k in range(nr[gl])) for gl in range(len(gs))]
-    if len(jobs) > slots:
-        raise ValueError(f"{len(jobs)} jobs for {slots} wave slots")
-    parts = [1] * len(jobs)
-    for _ in range(slots - len(jobs)):
-        j = max(range(len(jobs)), key=lambda x: (-(-sizes[x] // parts[x]), -x))
-        if sizes[j] <= parts[j]:
-            break  # no job left with more than one pair per wave
-        parts[j] += 1
-    waves = [[] for _ in gs]
-    for (gl, k), n, p in zip(jobs, sizes, parts):
-        if k is not None:
-            waves[gl] += [[(k, a, e)] for a, e in _split_even(n, p)]
-            continue
-        # a group: its relations' segments back to back, cut into p contiguous slices
-        lens = [tb.seg_len(gs[gl], kk, r) for kk in range(nr[gl])]
-        starts = np.cumsum([0] + lens)
-        for a, e in _split_even(n, p):
-            pieces = []
-            for kk in range(nr[gl]):
-                lo, hi = max(a, starts[kk]), min(e, starts[kk + 1])
-                if lo < hi:
-                    pieces.append((kk, int(lo - starts[kk]), int(hi - starts[kk])))
-            waves[gl].append(pieces)
-    return waves
-
-
 class PreparedSegTab(PreparedSeg):
     """The same launch as PreparedSeg (dg_spmm_seg_f32's workgroups in its XCD-contiguous item
     order, waves and chunk partials — bit for bit) through dg_spmm_seg_tab_f32, from a wave
-    table built here once.  Shapes as PreparedFusedTab."""
+    table built once on the host (wavetable.seg_table).  Shapes as PreparedFusedTab."""
 
     def __init__(self, specs: Sequence[SegSpec], d_in: int, d_out: int):
         super().__init__(specs, d_in, d_out)
-        if not _tab_shape(d_in, d_out, specs):
+        if not wavetable._tab_shape(d_in, d_out, specs):
             raise ValueError("dg_spmm_seg_tab_f32: d_in = d_out = 64, or 64 -> 32 with weight stacks")
-        live = [g for g, s in enumerate(specs) if s.n_rows > 0 and s.n_rels > 0]
-        nw = max([1] + [specs[g].chunk for g in live])
-        stride = 8 if nw <= 8 else 16
-        blocks = []  # (spec, chunk c, first row, rows per workgroup) or None (a dead workgroup)
-        for g in live:
-            s = specs[g]
-            rpb = nw // s.chunk
-            row_blocks = -(-s.n_rows // rpb)
-            items = s.n_chunks * row_blocks
-            n_blocks = 8 * (-(-items // 8))
-            per = n_blocks >> 3
-            for lb in range(n_blocks):
-                item = (lb & 7) * per + (lb >> 3)
-                blocks.append(None if item >= items else (g, item // row_blocks, (item % row_blocks) * rpb, rpb))
-        tb = _WaveTable(specs, len(blocks) * stride, d_out != d_in)
-        for b, blk in enumerate(blocks):
-            if blk is None:
-                continue
-            g, c, r0, rpb = blk
-            s = specs[g]
-            for w in range(nw):
-                i = b * stride + w
-                slot, t = divmod(w, s.chunk)
-                r = r0 + slot
-                if not (slot < rpb and r < s.n_rows):
-                    continue
-                k = c * s.chunk + t
-                if k < s.n_rels:
-                    tb.relation(i, g, k, r)
-                if t == 0:
-                    tb.desc["orow"][i] = s.out.data_ptr() + (c * s.n_rows + r) * d_out * 4
-                    tb.desc["role"][i] = s.chunk << 8
-        self._tab = tb.upload(self, len(blocks), nw, stride, specs[0].x.device)
-        self.n_blocks, self.nw = len(blocks), nw
+        self._tab = _upload_table(self, wavetable.seg_table([_seg_data(s) for s in specs], d_in, d_out,
+                                                            slot=knob("DG_TAB_SLOT", 0)), specs[0].x.device)
         self._tfn = _lib.load().dg_spmm_seg_tab_f32
 
     def __call__(self, stream=None) -> None:
@@ -808,9 +498,6 @@ class PreparedSegTab(PreparedSeg):
     def seg_form(self, stream=None) -> None:
         """The same partials through dg_spmm_seg_f32 (tests: bitwise equal)."""
         PreparedSeg.__call__(self, stream)
-
-
-DG_MAX_GROUPS_TAB = 8  # nbuf groups per row slot in gcn_tab_kernel (DG_MAX_GROUPS)
 
 
 @dataclass

@@ -237,7 +237,7 @@ int dg_gcn_fused_seg_f32(const dg_seg_group* groups /* HOST */, int32_t n_groups
 
 /* The wave-table form of dg_gcn_fused_seg_f32 (round 5): the same launch — workgroups, waves and
  * arithmetic — with everything a wave needs before its gathers precomputed on the host
- * (decagon_amd/kernels.py: _WaveTable, PreparedFusedTab) instead of found at run time from the
+ * (decagon_amd/wavetable.py; kernels.PreparedFusedTab uploads it) instead of found at run time from the
  * group and target arguments.  Wave w of workgroup b (slot i = b * nw_stride + w) reads desc[i]
  * and the first batch of its pairs (vcol, fp32 value bits: int32 pairs) in one round trip: the
  * first batch is compact, the S = slot_pairs pairs at pairs[S i .. S i + S - 1]; a wave with
@@ -246,17 +246,30 @@ int dg_gcn_fused_seg_f32(const dg_seg_group* groups /* HOST */, int32_t n_groups
  * handed out at once (4 at d_in 64, 8 at d_in 32), pair m < S of the wave sits at slot entry
  * (m % G) * S/G + m / G, and pair j of a later batch at entry (64/G) * (j % G) + j / G.
  * A wave with cnt 0 gathers nothing.  The wave whose desc.orow != NULL finishes that output row
- * alone after the workgroup's barrier: wr = group count | relu << 8 | row slot << 16,
- * pad[2] = (wave count - 1) of group u in bits 4u .. 4u + 3, pad[3] = the row slot's first wave;
- * it adds each group's waves in order, L2-normalises the group sums, adds them in order, applies
- * relu and stores the row.  The rows are bitwise dg_gcn_fused_seg_f32's only for a table with one
- * wave per relation; a table that deals a group's pairs over several waves (PreparedFusedTab's
- * balance) re-associates the group's fp32 sum.  desc.role is not read by dg_gcn_fused_tab_f32 or
- * its peer form (the host builder still records the round-5 normalising role in bits 0-20 and 31);
- * dg_gcn_fused_tab_post_f32 reads bits 24-27 and 30, dg_gcn_fused_tab_dec_f32 bit 29, and dg_spmm_seg_tab_f32 bits 8-15, as described
- * with them.  pad[0..1] belong to the peer form (below) or, in a projecting table, hold the P
- * row's address, or, on a flagged finishing wave of dg_gcn_fused_tab_dec_f32's table, the Q row's;
- * pad[4] is unused.
+ * alone after the workgroup's barrier: wr holds the row's group count, its relu bit and its row
+ * slot (DG_TAB_WR_*), gwaves the (wave count - 1) of group u in bits 4u .. 4u + 3, first_wave the
+ * row slot's first wave; it adds each group's waves in order, L2-normalises the group sums, adds
+ * them in order, applies relu and stores the row.  The rows are bitwise dg_gcn_fused_seg_f32's only
+ * for a table with one wave per relation; a table that deals a group's pairs over several waves
+ * (PreparedFusedTab's balance) re-associates the group's fp32 sum.
+ *
+ * Which entry point reads which field beyond x, w, orow, cnt, x_ld and ovf (all of them), and
+ * what the auxiliary words (aux_lo, aux_hi: the low and high half of one 64-bit value, or two
+ * 32-bit values) hold; the builder writes nothing else:
+ *
+ *   entry point                 role                        wr, gwaves, first_wave  aux_lo, aux_hi
+ *   dg_gcn_fused_tab_f32        -                           finishing wave          -
+ *   dg_gcn_fused_tab_peer_f32   -                           finishing wave          finishing wave: the row's byte
+ *                                                                                   offset in its target, the
+ *                                                                                   target's bytes
+ *   dg_gcn_fused_tab_post_f32   DG_TAB_ROLE_PROJ_BIT and    finishing wave          projecting wave: the address of
+ *                               the PROJ_SLOTS mask                                 row slot 0's P row
+ *   dg_gcn_fused_tab_dec_f32    DG_TAB_ROLE_DEC_BIT         finishing wave          flagged finishing wave: the
+ *                                                                                   address of the row's Q row
+ *   dg_spmm_seg_tab_f32         the SEG_WAVES field         -                       -
+ *
+ * Every finishing wave of a fused table carries the peer form's two values unless a projection
+ * job or a decoder row of the same wave needs the words (neither form has an exchange).
  * Shapes: d_in = d_out = 64; d_in = 64, d_out = 32 with W slabs (desc.w: the aggregate times the
  * relation's slab, so such a wave holds pairs of one relation); d_in = d_out = 32 (no exchange
  * form).  Replaces layers.py:85-94 / 109-118 and model.py:74-75, 85-88 as dg_gcn_fused_seg_f32
@@ -269,10 +282,29 @@ typedef struct dg_tab_desc {
     int32_t cnt;          /* pairs of the wave (0: none)                                     */
     int32_t x_ld;         /* floats                                                          */
     int32_t ovf;          /* first entry of the later batches in ovf                         */
-    uint32_t role;        /* see above                                                       */
-    uint32_t wr;
-    int32_t pad[5];
+    uint32_t role;        /* DG_TAB_ROLE_* below                                             */
+    uint32_t wr;          /* finishing wave: DG_TAB_WR_* below                               */
+    int32_t aux_lo;       /* the auxiliary value (table above), low half or first value      */
+    int32_t aux_hi;       /* high half or second value                                       */
+    int32_t gwaves;       /* finishing wave: the groups' wave counts, DG_TAB_GWAVES_BITS each */
+    int32_t first_wave;   /* finishing wave: the first wave of its row slot                  */
+    int32_t reserved;     /* 0                                                               */
 } dg_tab_desc;            /* 64 bytes                                                        */
+
+/* dg_tab_desc.role */
+#define DG_TAB_ROLE_PROJ_BIT 30         /* the wave holds a projection job (..._tab_post_f32)   */
+#define DG_TAB_ROLE_PROJ_SLOTS_SHIFT 24 /* the job's row slots: a mask of                       */
+#define DG_TAB_ROLE_PROJ_SLOTS_BITS 4   /* DG_TAB_MAX_ROW_SLOTS bits                            */
+#define DG_TAB_ROLE_DEC_BIT 29          /* the finishing wave also stores its Q row (..._dec_f32) */
+#define DG_TAB_ROLE_SEG_WAVES_SHIFT 8   /* dg_spmm_seg_tab_f32: the waves the first wave of a    */
+#define DG_TAB_ROLE_SEG_WAVES_BITS 8    /* (chunk, row) sums, itself included                    */
+/* dg_tab_desc.wr */
+#define DG_TAB_WR_GROUPS_BITS 8         /* bits 0-7: the row's groups                           */
+#define DG_TAB_WR_RELU_BIT 8            /* relu the finished row                                */
+#define DG_TAB_WR_SLOT_SHIFT 16         /* bits 16 and up: the row slot                         */
+/* dg_tab_desc.gwaves: (wave count - 1) of group u in bits 4u .. 4u + 3 */
+#define DG_TAB_GWAVES_BITS 4
+#define DG_TAB_MAX_ROW_SLOTS 4          /* rows a workgroup finishes, at most                   */
 
 typedef struct dg_wave_table {
     const int32_t* pairs; /* device, [n_blocks * nw_stride * slot_pairs][2], 16-byte aligned */
@@ -291,9 +323,9 @@ int dg_gcn_fused_tab_f32(const dg_wave_table* table /* HOST */, int32_t d_in, in
  * makes layer 2's operands P_k = H1_j·W2_k (layers.py:113, the reference's own order: matmul,
  * then the sparse product) in the workgroup that finishes the H1 row.  The finishing wave also
  * leaves its row (after relu, as stored) in LDS; after one more barrier every wave whose
- * desc.role has bit 30 set multiplies the row of each row slot s in the mask (role >> 24) & 15
+ * desc.role has DG_TAB_ROLE_PROJ_BIT set multiplies the row of each row slot s in its PROJ_SLOTS mask
  * by the [64][32] slab at desc.w and stores the 32 floats at A + 128 s bytes, A the 16-byte
- * aligned address in pad[0] (low half) and pad[1] (high half): row slot 0's P row (the rows of a
+ * aligned address in aux_lo (low half) and aux_hi (high half): row slot 0's P row (the rows of a
  * workgroup are consecutive).  A wave may hold a gather job, a projection job, both or neither; a
  * job names only row slots whose finishing wave exists in the same workgroup.  The H1 rows are
  * bitwise dg_gcn_fused_tab_f32's of the same table.  The table itself cannot say that it carries
@@ -303,8 +335,8 @@ int dg_gcn_fused_tab_post_f32(const dg_wave_table* table /* HOST */, int32_t d_i
 
 /* dg_gcn_fused_tab_f32 for a d_in = d_out = 32 table (layer 2 over pre-projected operands) that
  * also makes the DEDICOM decoder's row operands: the finishing wave of a row whose desc.role has
- * bit 29 set stores, after the row itself, Q[r] = l ∘ ((row ∘ l)·G) — 32 floats at the 16-byte
- * aligned address in pad[0] (low half) and pad[1] (high half) — so that a score is the dot
+ * DG_TAB_ROLE_DEC_BIT set stores, after the row itself, Q[r] = l ∘ ((row ∘ l)·G) — 32 floats at the
+ * 16-byte aligned address in aux_lo (low half) and aux_hi (high half) — so that a score is the dot
  * product Q[r]·E[c] (dg_decoder_hinge_rows_f32).  G is [32][32] row-major, l [32] or NULL (all
  * ones), both device, 16-byte aligned (DG_EALIGN otherwise).  The summation order is fixed: Q is
  * bitwise reproducible, and the rows are bitwise dg_gcn_fused_tab_f32's of the same table.  Other
@@ -313,8 +345,8 @@ int dg_gcn_fused_tab_dec_f32(const dg_wave_table* table /* HOST */, int32_t d_in
                              const float* l, void* stream);
 
 /* dg_gcn_fused_tab_f32 with the peer-store exchange (config S at N = 2 with --exchange peer):
- * every finished row also goes to every peer's copy of its target — desc.pad[0] = the row's
- * byte offset in its target, desc.pad[1] = the target's bytes, the target inside the exchange
+ * every finished row also goes to every peer's copy of its target — desc.aux_lo = the row's
+ * byte offset in its target, desc.aux_hi = the target's bytes, the target inside the exchange
  * region — and the launch ends with the exchange, as dg_gcn_fused_seg_peer_f32.  xchg as
  * dg_peer_allgather; at least one workgroup. */
 struct dg_peer_xchg;
@@ -324,8 +356,8 @@ int dg_gcn_fused_tab_peer_f32(const dg_wave_table* table /* HOST */, int32_t d_i
 /* The wave-table form of dg_spmm_seg_f32 (partial mode; config S's N-GPU layers): the same
  * workgroups (in that entry point's XCD-contiguous item order), waves and chunk partials, bit
  * for bit, from a host-built table with the layout above.  A wave whose desc.orow != NULL is
- * the first wave of its (chunk, row): after the barrier it adds the (desc.role >> 8) & 0xff
- * waves from itself on, in order, and stores the partial row there.  Shapes as above. */
+ * the first wave of its (chunk, row): after the barrier it adds the waves of desc.role's
+ * SEG_WAVES field from itself on, in order, and stores the partial row there.  Shapes as above. */
 int dg_spmm_seg_tab_f32(const dg_wave_table* table /* HOST */, int32_t d_in, int32_t d_out, void* stream);
 
 /* --------------------------------------------------------------------------------------

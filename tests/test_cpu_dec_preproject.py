@@ -1,6 +1,6 @@
 """Host side of the decoder's row operands (DG_DEC_PREPROJECT): the argument checks of
 dg_gcn_fused_tab_dec_f32 and dg_decoder_hinge_rows_f32, which run before any HIP call, and the
-wave-table flagging kernels._mark_dec_rows.
+wave-table flagging wavetable._mark_dec_rows.
 """
 import ctypes
 
@@ -68,32 +68,36 @@ def test_rows_hinge_entry_point_rejects_bad_arguments():
 
 
 def test_dec_flag_sits_on_exactly_the_finishing_waves():
-    """_mark_dec_rows: role bit 29 and the Q row's address on wave w < rows-per-workgroup of the
+    """_mark_dec_rows: the decoder-row role bit and the Q row's address on wave w < rows-per-workgroup of the
     attached target's workgroups, when the target has row first + w — config S's geometry at odd
     row counts (two gene rows a workgroup, one drug row), attached at either node type."""
-    from decagon_amd.kernels import DEC_ROLE_BIT, _mark_dec_rows, _tab_geometry, _WaveTable
+    from decagon_amd.wavetable import (DESC, DG_TAB_ROLE_DEC_BIT, _mark_dec_rows, _tab_geometry, decode_role,
+                                       encode_role, join_addr)
 
-    assert DEC_ROLE_BIT == 29
+    assert DG_TAB_ROLE_DEC_BIT == 29
+    other = encode_role(proj_slots=(1,))
     n_rows = [151, 97]
     nw, stride, rpbs = _tab_geometry([3, 7], True)
     plan = [(t, r0, rpbs[t]) for t in (0, 1) for r0 in range(0, n_rows[t], rpbs[t])]
     q_ptr = (5 << 32) + 0xfff00000  # the low half has its top bit set, the high half is not zero
     for target in (0, 1):
-        desc = np.zeros(len(plan) * stride, _WaveTable.DESC)
-        desc["role"] = 1 << 31  # (bits of other roles stay)
-        desc["pad"][:, 2] = 7
+        desc = np.zeros(len(plan) * stride, DESC)
+        desc["role"] = other  # (bits of other roles stay)
+        desc["gwaves"] = 7
         assert _mark_dec_rows(desc, plan, stride, target, n_rows[target], q_ptr) == n_rows[target]
         seen = []
         for b, (t, r0, rpb) in enumerate(plan):
             for w in range(stride):
                 d = desc[b * stride + w]
-                flagged = bool((int(d["role"]) >> DEC_ROLE_BIT) & 1)
+                flagged = bool((int(d["role"]) >> DG_TAB_ROLE_DEC_BIT) & 1)
+                assert decode_role(d["role"]).dec == flagged
                 assert flagged == (t == target and w < rpb and r0 + w < n_rows[t]), (b, w)
-                assert int(d["role"]) >> 31 == 1 and d["pad"][2] == 7
+                assert int(d["role"]) & ~encode_role(dec=True) == other and d["gwaves"] == 7
                 if flagged:
-                    addr = (int(np.uint32(d["pad"][1])) << 32) | int(np.uint32(d["pad"][0]))
+                    addr = join_addr(d["aux_lo"], d["aux_hi"])
+                    assert addr == (int(np.uint32(d["aux_hi"])) << 32) | int(np.uint32(d["aux_lo"]))
                     assert addr == q_ptr + 128 * (r0 + w) and addr % 16 == 0
                     seen.append(r0 + w)
                 else:
-                    assert d["pad"][0] == 0 and d["pad"][1] == 0
+                    assert d["aux_lo"] == 0 and d["aux_hi"] == 0
         assert seen == list(range(n_rows[target]))  # every row once

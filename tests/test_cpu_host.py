@@ -479,10 +479,10 @@ def test_bool_knob_rejects_other_values(monkeypatch):
 
 @pytest.mark.parametrize("proj", [False, True])
 def test_balanced_wave_dealing_covers_every_pair_once(proj):
-    """PreparedFusedTab(balance=True)'s host dealing (kernels._balanced_waves): every pair of every
+    """PreparedFusedTab(balance=True)'s host dealing (wavetable._balanced_waves): every pair of every
     relation lands in exactly one wave, in relation order within a group; a reassociated wave
     (proj) holds one relation only; the waves fit the row's slots and the longest share shrinks."""
-    from decagon_amd.kernels import _balanced_waves
+    from decagon_amd.wavetable import _balanced_waves
 
     rng = np.random.default_rng(5)
     for trial in range(50):

@@ -1,5 +1,5 @@
 """Host side of layer 1's projection jobs (PreparedFusedTab(projs=...), DG_L2_PREPROJECT): the
-pure job assignment kernels._proj_jobs / tab_proj_fit, and dg_gcn_fused_tab_post_f32's argument
+pure job assignment wavetable._proj_jobs / tab_proj_fit, and dg_gcn_fused_tab_post_f32's argument
 checks, which run on the host before any HIP call.
 """
 import ctypes
@@ -11,7 +11,7 @@ torch = pytest.importorskip("torch")
 
 
 def test_every_row_relation_gets_exactly_one_wave():
-    from decagon_amd.kernels import _proj_jobs
+    from decagon_amd.wavetable import _proj_jobs
 
     rng = np.random.default_rng(5)
     fitted = refused = 0
@@ -55,7 +55,7 @@ def test_every_row_relation_gets_exactly_one_wave():
 def test_config_S_jobs_fill_the_idle_waves():
     """Config S: drug rows (one row a workgroup) take 7 jobs in waves 1-7, gene rows (two rows a
     workgroup) 2 x 3 in waves 2-7; the last gene workgroup of an odd row count projects one row."""
-    from decagon_amd.kernels import _proj_jobs, _tab_geometry, tab_proj_fit
+    from decagon_amd.wavetable import _proj_jobs, _tab_geometry, tab_proj_fit
 
     for balance in (False, True):
         nw, stride, rpbs = _tab_geometry([3, 7], balance)
@@ -74,7 +74,7 @@ def test_config_S_jobs_fill_the_idle_waves():
 
 
 def test_form_refused_when_jobs_do_not_fit():
-    from decagon_amd.kernels import _proj_jobs, tab_proj_fit
+    from decagon_amd.wavetable import _proj_jobs, tab_proj_fit
 
     assert _proj_jobs([True, True], 5, 8) is None
     assert _proj_jobs([True, False], 5, 8) is None  # the full workgroup decides, not this one's rows

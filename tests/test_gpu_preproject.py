@@ -199,8 +199,11 @@ def test_p_stacks_exact_on_small_integers(share):
     plan = _plan(g, w1, w2, share=share)
     l1, _ = _forms(plan)
     assert l1.projs
-    masks = (l1._desc_v.cpu().numpy().view(np.uint32).reshape(-1, 16)[:, 9] >> 24) & 15  # role bits 24-27
-    assert (np.isin(masks, [3]).any()) == share  # two gene rows in one job only when shared
+    from decagon_amd import wavetable
+
+    desc = l1._desc_v.cpu().numpy().view(wavetable.DESC)
+    jobs = [wavetable.decode_role(r).proj_slots for r in desc["role"]]
+    assert any(jobs) and ((0, 1) in jobs) == share  # two gene rows in one job only when shared
     h1, _, p = _run(plan)
     n = g.n_nodes
     want_h1 = {t: np.zeros((n[t], 64), np.float64) for t in n}
