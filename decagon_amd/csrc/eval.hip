@@ -17,6 +17,7 @@
 // One workgroup per positive counts in integers (exact); the terms are summed in double, in
 // positive order, by one workgroup: deterministic.
 #include "common.h"
+#include "rank_metrics.h"
 
 namespace {
 
@@ -33,31 +34,11 @@ __device__ __forceinline__ int block_sum_int(int v, int* red) {
     return s;
 }
 
-// The score each edge is ranked by (mode, dg_rank_metrics_ex_f32), from its logit x:
-//   DG_RANK_LOGIT      x itself (float)
-//   DG_RANK_SIGMOID64  main.py:51-52,60,70,81 under numpy 1.14 (requirements.txt:14): rec is
-//                      TF's float32, so np.exp(-x) runs in float32 (glibc expf: correctly
-//                      rounded — computed here as (float)exp((double)-x)), `1 + e` and `1. / …`
-//                      promote to float64, then np.nan_to_num.  Saturates: x > ≈36.7 → 1.0,
-//                      x < ≈-88.7 → 0.0 (float32 exp overflows), so large logits tie.
-//   DG_RANK_SIGMOID32  MathUtils.sigmoid on the float32 decoder output array
-//                      (DecagonAccuracyEvaluator.py:123): every step float32 (x > ≈16.6 → 1.0)
+// key[i] = the score logit x[i] is ranked by (dg::score_key, rank_metrics.h)
 __global__ __launch_bounds__(256) void score_key_kernel(const float* x, int n, int mode, double* key) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float v = x[i];
-    double k = v;
-    if (mode != DG_RANK_LOGIT) {
-        const float e = (float)exp(-(double)v);
-        if (mode == DG_RANK_SIGMOID64) {
-            k = 1.0 / (1.0 + (double)e);
-        } else {
-            const float one = 1.0f;
-            k = (double)(one / (one + e));
-        }
-        if (k != k) k = 0.0;  // np.nan_to_num (only a NaN logit gets here)
-    }
-    key[i] = k;
+    key[i] = dg::score_key(x[i], mode);
 }
 
 // counts[i] = {lt_neg, eq_neg, ge_pos, ge_all, gt_all, gt_pos, eq_pos_before}
@@ -83,42 +64,12 @@ __global__ __launch_bounds__(256) void rank_counts_kernel(const T* pos, int P, c
     int c[6] = {lt_neg, eq_neg, ge_pos, gt_pos, eq_before, gt_neg};
 #pragma unroll
     for (int q = 0; q < 6; ++q) c[q] = block_sum_int(c[q], red);
-    if (threadIdx.x == 0) {
-        int* o = counts + (int64_t)i * 8;
-        o[0] = c[0];                   // #neg < s
-        o[1] = c[1];                   // #neg == s
-        o[2] = c[2];                   // #pos >= s
-        o[3] = c[2] + c[1] + c[5];     // #all >= s
-        o[4] = c[3] + c[5];            // #all > s
-        o[5] = c[3];                   // #pos > s
-        o[6] = c[4];                   // #pos before i with == s
-    }
+    if (threadIdx.x == 0) dg::rank_record(counts + (int64_t)i * 8, c[0], c[1], c[2], c[3], c[4], c[5]);
 }
 
 __global__ __launch_bounds__(256) void rank_reduce_kernel(const int* counts, int P, int N, int k, double* out) {
     __shared__ double red[3][256];
-    double au = 0.0, ap = 0.0, apk = 0.0;
-    for (int i = threadIdx.x; i < P; i += 256) {
-        const int* c = counts + (int64_t)i * 8;
-        au += (double)c[0] + 0.5 * (double)c[1];
-        ap += (double)c[2] / (double)c[3];
-        const int rank = c[4] + c[6];
-        if (rank < k) apk += ((double)(c[5] + c[6]) + 1.0) / ((double)rank + 1.0);
-    }
-    red[0][threadIdx.x] = au;
-    red[1][threadIdx.x] = ap;
-    red[2][threadIdx.x] = apk;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w)
-            for (int q = 0; q < 3; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out[0] = N > 0 && P > 0 ? red[0][0] / ((double)P * (double)N) : __builtin_nan("");
-        out[1] = P > 0 ? red[1][0] / (double)P : __builtin_nan("");
-        out[2] = P > 0 ? red[2][0] / (double)(P < k ? P : k) : 0.0;
-    }
+    dg::rank_reduce_block(counts, P, N, k, out, red);
 }
 
 }  // namespace

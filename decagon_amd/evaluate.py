@@ -18,6 +18,12 @@ resulting ties move AUROC, AUPRC and AP@k.  `sigmoid` selects the reference's fo
   "evaluator"  DecagonAccuracyEvaluator (MathUtils.sigmoid on the float32 decoder output,
                DecagonAccuracyEvaluator.py:123): all float32, logits > ≈16.6 score 1.0
   None         the raw logits
+
+accuracy_scores serves one relation per call.  accuracy_scores_all evaluates every relation of
+an edge type — the reference's loop over edge_type2idx, DecagonAccuracyEvaluator.evaluateAll —
+in one pass: the sampled pairs of all relations packed into segments (pack_edge_samples), one
+scorer launch (dg_decoder_score_seg_f32) and one segmented metrics call
+(dg_rank_metrics_seg_f32), row for row the bits of the per-relation call.
 """
 from __future__ import annotations
 
@@ -191,3 +197,145 @@ def accuracy_scores(sess, opt, placeholders, feed_dict, edges_pos, edges_neg, ed
 
     au, ap, apk = sess.run(Node("evaluate/accuracy", fn), feed_dict=fd).tolist()
     return au, ap, apk
+
+
+def rank_metrics_seg_device(pos: torch.Tensor, pos_ptr: torch.Tensor, neg: torch.Tensor, neg_ptr: torch.Tensor,
+                            k: int = 50, sigmoid: Optional[str] = "main") -> torch.Tensor:
+    """float64 device tensor [n_seg, 3]: row s = [AUROC, AUPRC, AP@k] of the positive logits
+    pos[pos_ptr[s]:pos_ptr[s+1]] against the negative logits neg[neg_ptr[s]:neg_ptr[s+1]]
+    (dg_rank_metrics_seg_f32) — bit for bit rank_metrics_device on that segment alone, for all
+    segments in three launches.  pos_ptr / neg_ptr: device int32 [n_seg + 1], ascending from 0 to
+    the length of pos / neg; they are not read on the host (asynchronous, graph-capturable)."""
+    if sigmoid not in SIGMOID_MODES:
+        raise ValueError(f"sigmoid must be one of {list(SIGMOID_MODES)}")
+    if int(k) < 1:
+        raise ValueError("k must be at least 1")
+    for t, nm in ((pos, "pos"), (neg, "neg")):
+        kernels._dev(t, torch.float32, nm)
+    for t, nm in ((pos_ptr, "pos_ptr"), (neg_ptr, "neg_ptr")):
+        kernels._dev(t, torch.int32, nm)
+    n_seg = pos_ptr.numel() - 1
+    if n_seg < 1 or neg_ptr.numel() != n_seg + 1:
+        raise ValueError("pos_ptr and neg_ptr must both have n_seg + 1 >= 2 entries")
+    lib = _lib.load()
+    P, N = pos.numel(), neg.numel()
+    nbytes = int(lib.dg_rank_metrics_seg_workspace(P, N, n_seg))
+    ws = torch.empty(-(-nbytes // 8), dtype=torch.float64, device=pos_ptr.device)
+    out = torch.empty((n_seg, 3), dtype=torch.float64, device=pos_ptr.device)
+    check(lib.dg_rank_metrics_seg_f32(pos.data_ptr() if P else None, pos_ptr.data_ptr(), P,
+                                      neg.data_ptr() if N else None, neg_ptr.data_ptr(), N, n_seg, int(k),
+                                      SIGMOID_MODES[sigmoid], out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                      kernels._stream_ptr(None)), "dg_rank_metrics_seg_f32")
+    return out
+
+
+def _relation_samples(edges, ij, r) -> np.ndarray:
+    """The [n, 2] int64 samples of relation r in edges[ij] (a sequence or a mapping by relation);
+    a missing relation, None or an empty array give [0, 2]."""
+    per = edges.get(ij) if hasattr(edges, "get") else edges[ij]
+    e = None
+    if per is not None:
+        if hasattr(per, "get"):
+            e = per.get(r)
+        elif 0 <= r < len(per):
+            e = per[r]
+    if e is None:
+        return np.zeros((0, 2), np.int64)
+    return np.asarray(e, dtype=np.int64).reshape(-1, 2)
+
+
+def pack_edge_samples(edges_pos, edges_neg, edge_type_ij, num_relations: int, shape, relations=None):
+    """The sampled edges of the relations of edge type (i, j), packed for one fused evaluation
+    (host only): (row_idx, col_idx, pos_ptr, neg_ptr, relations), all numpy int32.
+
+    row_idx / col_idx hold the positives of every listed relation, relation by relation in the
+    order of `relations` (default: 0 .. num_relations − 1), then the negatives in the same order;
+    relation relations[s]'s positives are row_idx[pos_ptr[s]:pos_ptr[s+1]] and its negatives
+    row_idx[P + neg_ptr[s] : P + neg_ptr[s+1]] with P = pos_ptr[-1].  edges_pos / edges_neg are
+    get_accuracy_scores' (main.py:38-80): edges[(i, j)][r] = an [n, 2] array; a relation that is
+    missing, None or empty gives an empty segment.  An index outside `shape` = (N_i, N_j), or a
+    relation outside [0, num_relations), raises ValueError."""
+    ij = tuple(edge_type_ij)
+    rels = np.arange(num_relations, dtype=np.int64) if relations is None else np.asarray(relations, np.int64).reshape(-1)
+    if rels.size < 1:
+        raise ValueError("no relations to evaluate")
+    if rels.min() < 0 or rels.max() >= num_relations:
+        raise ValueError(f"relation outside [0, {num_relations})")
+    parts, ptrs = [], []
+    for edges in (edges_pos, edges_neg):
+        chunks = [_relation_samples(edges, ij, int(r)) for r in rels]
+        ptr = np.zeros(rels.size + 1, np.int64)
+        np.cumsum([len(c) for c in chunks], out=ptr[1:])
+        parts.append(np.concatenate(chunks) if chunks else np.zeros((0, 2), np.int64))
+        ptrs.append(ptr)
+    allp = np.concatenate(parts)
+    if allp.shape[0] >= 2**31 - 64 * (2 * rels.size + 1):
+        raise ValueError("too many samples for 32-bit offsets")
+    if allp.size and (allp.min() < 0 or allp[:, 0].max() >= shape[0] or allp[:, 1].max() >= shape[1]):
+        raise ValueError("edge sample outside the embedding tables")
+    return (np.ascontiguousarray(allp[:, 0], np.int32), np.ascontiguousarray(allp[:, 1], np.int32),
+            ptrs[0].astype(np.int32), ptrs[1].astype(np.int32), rels.astype(np.int32))
+
+
+def accuracy_scores_all(sess, opt, placeholders, feed_dict, edges_pos, edges_neg, edge_type_ij, relations=None,
+                        k: int = 50, sigmoid: Optional[str] = "main", pooled: bool = False):
+    """get_accuracy_scores (main.py:38-80) for ALL relations of edge type (i, j) in one fused pass:
+    numpy float64 [K, 3], row s = (roc, auprc, apk@k) of relation relations[s] (default: every
+    relation of the edge type, in order) — exactly what accuracy_scores returns for it.
+
+    What the reference's final loop over edge_type2idx and DecagonAccuracyEvaluator.evaluateAll
+    (DecagonAccuracyEvaluator.py:57-91) do one relation at a time: here one sess.run at dropout 0,
+    one upload of the packed sample indices (pack_edge_samples), one scorer launch over the 2·K
+    segments (dg_decoder_score_seg_f32: positives, then negatives), one segmented metrics call
+    (dg_rank_metrics_seg_f32) and one copy back.  The decoder's variables are read in place for
+    all four decoder types, so a fed latent matrix is refused, as in top_candidates.
+
+    pooled=True also returns (auroc, auprc) of the samples of all listed relations concatenated —
+    evaluateAll's pooled figures (DecagonAccuracyEvaluator.py:73-91) — as a second value:
+    (scores [K, 3], (auroc, auprc)).  It is the same entry point with a single segment over the
+    already contiguous score arrays, and it is off by default: its cost grows with
+    P_total·(P_total + N_total), and it has NOT been measured at the polypharmacy shape."""
+    if sigmoid not in SIGMOID_MODES:
+        raise ValueError(f"sigmoid must be one of {list(SIGMOID_MODES)}")
+    i, j = edge_type_ij
+    model = opt._model()
+    if (i, j) not in model.edge_type2decoder:
+        raise ValueError(f"unknown edge type {(i, j)}")
+    dec = model.edge_type2decoder[i, j]
+    K = dec.num_types
+    fd = dict(feed_dict)
+    fd[placeholders["dropout"]] = 0.0
+
+    def fn(ctx: RunContext):
+        ets = list(model.edge_types)
+        first = sum(model.edge_types[et] for et in ets[:ets.index((i, j))])  # flat index of relation 0
+        for r in range(first, first + K):
+            if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
+                raise ValueError("accuracy_scores_all reads the decoder's variables; a latent matrix is fed")
+        row_t, col_t = opt._tables(ctx, i, j)
+        G, l = _stacked_latents(ctx, dec, row_t.shape[1])
+        ri, ci, pos_ptr, neg_ptr, rels = pack_edge_samples(edges_pos, edges_neg, (i, j), K,
+                                                           (row_t.shape[0], col_t.shape[0]), relations)
+        n_seg, P, N = rels.size, int(pos_ptr[-1]), int(neg_ptr[-1])
+        # one upload: [row_idx | col_idx | seg_ptr (2·n_seg + 1) | seg_rel (2·n_seg) | neg_ptr | 0, P | 0, N]
+        seg_ptr = np.concatenate([pos_ptr, P + neg_ptr[1:]])
+        host = np.concatenate([ri, ci, seg_ptr, rels, rels, neg_ptr, [0, P], [0, N]]).astype(np.int32)
+        buf = torch.from_numpy(host).to(ctx.session.device)
+        n = P + N
+        o = 2 * n
+        d_ri, d_ci = buf[:n], buf[n:o]
+        d_seg, o = buf[o:o + 2 * n_seg + 1], o + 2 * n_seg + 1
+        d_rel, o = buf[o:o + 2 * n_seg], o + 2 * n_seg
+        d_neg, o = buf[o:o + n_seg + 1], o + n_seg + 1
+        d_pos = d_seg[:n_seg + 1]
+        scores = kernels.decoder_score_seg(row_t, col_t, d_ri, d_ci, d_seg, G, l, seg_rel=d_rel)
+        per = rank_metrics_seg_device(scores[:P], d_pos, scores[P:], d_neg, k, sigmoid)
+        if not pooled:
+            return per
+        allm = rank_metrics_seg_device(scores[:P], buf[o:o + 2], scores[P:], buf[o + 2:o + 4], k, sigmoid)
+        return torch.cat([per, allm])
+
+    res = np.asarray(sess.run(Node("evaluate/accuracy_all", fn), feed_dict=fd), np.float64)
+    if not pooled:
+        return res
+    return res[:-1], (float(res[-1, 0]), float(res[-1, 1]))

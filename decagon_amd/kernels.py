@@ -1115,6 +1115,80 @@ def decoder_score(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: tor
     return out
 
 
+def decoder_score_seg(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: torch.Tensor,
+                      col_idx: torch.Tensor, seg_ptr: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor],
+                      seg_rel: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      stream=None) -> torch.Tensor:
+    """Scores of pairs packed by segment, every segment with its own relation, in one launch
+    (dg_decoder_score_seg_f32): for pair p of segment s = [seg_ptr[s], seg_ptr[s+1]) and
+    k = seg_rel[s] (seg_rel None: k = s),
+        out[p] = (row_table[row_idx[p]] ∘ l_k)ᵀ · G_k · (l_k ∘ col_table[col_idx[p]])
+    — bit for bit decoder_score(…, G_k, l_k) on the segment's pairs.  Asynchronous; seg_ptr
+    (device int32 [n_seg + 1], ascending from 0 to the pair count) is never read on the host.
+
+    G: [d, d] (shared by every relation) or [K, d, d]; l: None (identity), [d] (shared) or [K, d];
+    K is the leading dimension of whichever is per relation.  seg_rel: device int32 [n_seg] with
+    values in [0, K).  A pair outside the tables, or a segment whose relation is outside [0, K),
+    scores NaN."""
+    tabs = [(row_table, "row_table"), (col_table, "col_table"), (G, "G")] + ([(l, "l")] if l is not None else [])
+    idx = [(row_idx, "row_idx"), (col_idx, "col_idx"), (seg_ptr, "seg_ptr")] + (
+        [(seg_rel, "seg_rel")] if seg_rel is not None else [])
+    for ts, dt in ((tabs, torch.float32), (idx, torch.int32)):
+        for t, nm in ts:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{nm}: expected a torch.Tensor, got {type(t).__name__}")
+            if t.dtype != dt:
+                raise TypeError(f"{nm}: dtype {t.dtype}, expected {dt}")
+            if not t.is_contiguous():
+                raise ValueError(f"{nm}: must be contiguous")
+    if row_table.dim() != 2 or col_table.dim() != 2 or G.dim() not in (2, 3):
+        raise ValueError("decoder_score_seg: tables must be [N, d] and G [d, d] or [K, d, d]")
+    d = G.shape[-1]
+    if G.shape[-2] != d or row_table.shape[1] != d or col_table.shape[1] != d:
+        raise ValueError("decoder_score_seg: d mismatch")
+    if l is not None and (l.dim() not in (1, 2) or l.shape[-1] != d):
+        raise ValueError("decoder_score_seg: d mismatch (l must be [d] or [K, d])")
+    if d < 32 or d % 32 or d > 256:
+        raise ValueError(f"decoder_score_seg: d = {d} unsupported (a multiple of 32, at most 256)")
+    n_rows, n_cols = row_table.shape[0], col_table.shape[0]
+    if n_rows < 1 or n_cols < 1:
+        raise ValueError("decoder_score_seg: empty table")
+    n = row_idx.numel()
+    if col_idx.numel() != n:
+        raise ValueError("decoder_score_seg: row_idx / col_idx length mismatch")
+    n_seg = seg_ptr.numel() - 1
+    if n_seg < 1:
+        raise ValueError("decoder_score_seg: seg_ptr must have n_seg + 1 >= 2 entries")
+    if seg_rel is not None and seg_rel.numel() != n_seg:
+        raise ValueError("decoder_score_seg: seg_rel must have one entry per segment")
+    ks = {int(t.shape[0]) for t, per in ((G, G.dim() == 3), (l, l is not None and l.dim() == 2)) if per}
+    if len(ks) > 1:
+        raise ValueError(f"decoder_score_seg: relation counts disagree: {sorted(ks)}")
+    K = ks.pop() if ks else None  # None: no per-relation operand, any relation index serves
+    if K is not None and K < 1:
+        raise ValueError("decoder_score_seg: no relations")
+    if K is not None and seg_rel is None and n_seg > K:
+        raise ValueError(f"decoder_score_seg: {n_seg} segments but {K} relations (pass seg_rel)")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise TypeError("out: expected a contiguous float32 torch.Tensor")
+        if out.numel() != n:
+            raise ValueError("decoder_score_seg: out must have one entry per pair")
+    for t, nm in tabs + idx + ([(out, "out")] if out is not None else []):
+        if not t.is_cuda:
+            raise ValueError(f"{nm}: must be a device (HIP) tensor")
+    if out is None:
+        out = torch.empty(n, device=G.device, dtype=torch.float32)
+    n_rel = K if K is not None else (2**31 - 1 if seg_rel is not None else n_seg)
+    fn = _lib.load().dg_decoder_score_seg_f32
+    check(fn(row_table.data_ptr(), d, n_rows, col_table.data_ptr(), d, n_cols, row_idx.data_ptr() if n else None,
+             col_idx.data_ptr() if n else None, seg_ptr.data_ptr(), seg_rel.data_ptr() if seg_rel is not None else None,
+             n_seg, n, G.data_ptr(), d * d if G.dim() == 3 else 0, l.data_ptr() if l is not None else None,
+             d if (l is not None and l.dim() == 2) else 0, n_rel, d, out.data_ptr() if n else None,
+             _stream_ptr(stream)), "dg_decoder_score_seg_f32")
+    return out
+
+
 def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor],
                  topk: int, exclude=None, upper: bool = False, no_diag: bool = False, stream=None
                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:

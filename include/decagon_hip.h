@@ -37,7 +37,9 @@ extern "C" {
 #define DG_MAX_GROUPS 8
 
 /* ABI version (39); bumped whenever a struct layout or a signature changes or an entry point is added
- * (36: DG_PEER_STATE_WORDS grew; 39: dg_decoder_topk_f32). */
+ * (36: DG_PEER_STATE_WORDS grew; 39: dg_decoder_topk_f32).  Added since 39 without a bump, purely
+ * additive: dg_decoder_score_seg_f32, dg_rank_metrics_seg_workspace, dg_rank_metrics_seg_f32 and
+ * the host helper dg_seg_tile_lookup (evaluation of all relations of an edge type in one pass). */
 int32_t dg_abi_version(void);
 
 /* --------------------------------------------------------------------------------------
@@ -941,6 +943,57 @@ int dg_decoder_topk_f32(const float* row_table, int64_t ld_row, int32_t n_rows, 
                         const int32_t* excl_rowptr, const int32_t* excl_col, int32_t flags,
                         float* out_score, int32_t* out_row, int32_t* out_col, int32_t* out_count,
                         void* workspace, int64_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * Evaluation of all relations of one edge type in one pass (additive to ABI 39).
+ * Replaces the loop of get_accuracy_scores over every relation (main.py:38-80 and its final loop)
+ * and DecagonAccuracyEvaluator.evaluateAll (DecagonAccuracyEvaluator.py:57-91), which through
+ * dg_decoder_score_f32 + dg_rank_metrics_ex_f32 cost one set of launches and a host round trip
+ * per relation.
+ *
+ * Both entry points work on SEGMENTS of packed device arrays: segment s is elements
+ * [ptr[s], ptr[s+1]) with ptr int32 [n_seg + 1] ON THE DEVICE, ascending, ptr[0] = 0 and
+ * ptr[n_seg] = the total.  Neither reads ptr on the host: the calls are asynchronous and can be
+ * captured in a graph.  Segments may be empty.
+ *
+ * dg_decoder_score_seg_f32: for pair p of segment s with k = seg_rel[s] (seg_rel NULL: k = s),
+ *
+ *     out[p] = (row_table[row_idx[p]] ∘ l_k)ᵀ · G_k · (l_k ∘ col_table[col_idx[p]])
+ *
+ * with the operand conventions of dg_decoder_topk_f32 (G_k = G + k*g_stride, g_stride 0 or d*d;
+ * l_k = l + k*l_stride, l_stride 0 or d; l NULL = identity) and d as dg_decoder_score_f32
+ * (d % 32 == 0, d <= 256).  0 <= k < n_rel; without seg_rel, per-relation operands need
+ * n_seg <= n_rel.  n_pairs + 32*n_seg < 2^31.  One wave scores one 32-pair tile of one segment
+ * with the tile routine of dg_decoder_score_f32, so a segment's scores equal that entry point's
+ * on the segment's pairs with G_k, l_k bit for bit.  A pair whose index lies outside
+ * [0, n_rows) x [0, n_cols), and every pair of a segment whose relation lies outside [0, n_rel),
+ * scores NaN (nothing out of range is read).
+ *
+ * dg_rank_metrics_seg_f32: out[s][0..2] = {AUROC, AUPRC, AP@k} (double) of segment s's positive
+ * logits pos[pos_ptr[s] .. pos_ptr[s+1]) against its negative logits neg[neg_ptr[s] ..
+ * neg_ptr[s+1]), ranked under `mode` (DG_RANK_*) — bit for bit what dg_rank_metrics_ex_f32 returns
+ * for that segment alone, including its conventions for an empty class (no positives: NaN, NaN,
+ * 0.0; no negatives: AUROC NaN).  Workspace 16-byte aligned, dg_rank_metrics_seg_workspace(...)
+ * bytes (linear in the totals; 0 for negative arguments).
+ * n_pos_total + n_neg_total + 256*n_seg < 2^31.
+ *
+ * dg_seg_tile_lookup (HOST arrays; no device): the map both launches use to deal tiles of `tile`
+ * elements to segments without a prefix sum — segment s owns the virtual tiles starting at
+ * seg_ptr[s]/tile + s, the grid is seg_ptr[n_seg]/tile + n_seg.  For virtual tile vt it stores
+ * the segment and the tile's index inside it and returns 1, or 0 when that slot lies past the
+ * segment's end (the wave exits); DG_EINVAL for vt outside the grid or bad arguments.
+ * -------------------------------------------------------------------------------------- */
+int dg_decoder_score_seg_f32(const float* row_table, int64_t ld_row, int32_t n_rows, const float* col_table,
+                             int64_t ld_col, int32_t n_cols, const int32_t* row_idx, const int32_t* col_idx,
+                             const int32_t* seg_ptr, const int32_t* seg_rel, int32_t n_seg, int32_t n_pairs,
+                             const float* G, int64_t g_stride, const float* l, int64_t l_stride, int32_t n_rel,
+                             int32_t d, float* out, void* stream);
+int64_t dg_rank_metrics_seg_workspace(int32_t n_pos_total, int32_t n_neg_total, int32_t n_seg);
+int dg_rank_metrics_seg_f32(const float* pos, const int32_t* pos_ptr, int32_t n_pos_total, const float* neg,
+                            const int32_t* neg_ptr, int32_t n_neg_total, int32_t n_seg, int32_t k, int32_t mode,
+                            double* out, void* workspace, int64_t workspace_bytes, void* stream);
+int32_t dg_seg_tile_lookup(const int32_t* seg_ptr, int32_t n_seg, int32_t tile, int32_t vt, int32_t* seg,
+                           int32_t* local);
 
 /* --------------------------------------------------------------------------------------
  * Unigram negative sampler (T11):  out[i] ~ Categorical(p), p_c ∝ degree_c^0.75, draw
