@@ -770,7 +770,9 @@ extern "C" int dg_decoder_score_bf16_paired(const uint16_t* row_table, int64_t l
     if (!dg::aligned16(G)) return DG_EALIGN;  // R rows are staged into LDS in 16-byte pieces
     if (d == 256 && fits_32bit_offsets(n_row_table, ld_row) && fits_32bit_offsets(n_col_table, ld_col)) {
         // the 16x16x32 form (decoder_bf16_cs16_kernel, FUSED = false): bit-identical scores to
-        // dg_slot_score_hinge_bf16's; 32-bit byte offsets into the tables are required
+        // dg_slot_score_hinge_bf16's where that call runs this form too (batch % 32 == 0; its
+        // 32x32x16 fallback accumulates in another order); 32-bit byte offsets into the tables
+        // are required
         constexpr int kT16 = kCs16Threads;
         const int lds16 = d * d * 2;  // R
         int blocks16 = (n_tiles + kT16 / 64 - 1) / (kT16 / 64);

@@ -14,7 +14,13 @@ once with d = 256 bf16 embeddings and parameters (fp32 accumulation):
      negative share the column and the relation: T = R·(D_k∘v) is contracted once for both),
   3. relu(neg − pos + margin) is summed over the rank's pairs — 1-3 in ONE launch,
      dg_slot_score_hinge_bf16 (fused=False: dg_unigram_sample_slots, dg_decoder_score_bf16_paired
-     and dg_hinge_loss_ws_f32 as three launches, the same draws and scores), and
+     and dg_hinge_loss_ws_f32 as three launches: the same draws always; the same score bits
+     when both forms run one kernel template — batch % 32 == 0 with tables within 32-bit byte
+     offsets (the 16x16x32 kernel), or a table past them (the 32x32x16 kernel).  Otherwise the
+     fused call runs the 32x32x16 kernel and the paired call the 16x16x32 one: the same bf16
+     operands in another fp32 accumulation order, so the scores are equal where the sums are
+     exact and within fp32 accumulation rounding of each other elsewhere; the loss is summed
+     in another fixed order in every case.  tests/test_gpu_bf16_paths.py), and
   4. with N ranks, one all-reduce of that scalar — the only collective.
 
 Slots are dealt in contiguous blocks (sharding.slot_range); embeddings and parameters are

@@ -713,7 +713,13 @@ int dg_decoder_score_bf16_paired(const uint16_t* row_table, int64_t ld_row, int6
  * (left zero).  d == 256; G, tables and l_table 16-byte aligned.  Replaces optimizer.py:38-47
  * (fixed_unigram_candidate_sampler over the relation's degrees), :51-57 / :63-85 (batch_predict,
  * G = R, L = D_k: model.py:130-134) and :116-120 (_hinge_loss).  n_row_table / n_col_table:
- * the tables' row counts (range <= n_row_table), as for dg_decoder_score_bf16_paired. */
+ * the tables' row counts (range <= n_row_table), as for dg_decoder_score_bf16_paired.
+ * The scores are dg_decoder_score_bf16_paired's bit for bit when batch % 32 == 0 and both tables
+ * lie within 31-bit byte offsets (both calls run the 16x16x32 kernel), or when a table exceeds
+ * them (both run the 64-bit addressed 32x32x16 kernel).  With batch % 32 != 0 on small tables this
+ * call runs the 32x32x16 kernel (tiles may straddle slots; the last may be ragged) and the paired
+ * call the 16x16x32 one: the same bf16 operands, another fp32 accumulation order — equal where
+ * the sums are exact, else within fp32 accumulation rounding (tests/test_gpu_bf16_paths.py). */
 int dg_slot_score_hinge_bf16(const uint16_t* row_table, int64_t ld_row, int64_t n_row_table,
                              const uint16_t* col_table, int64_t ld_col, int64_t n_col_table,
                              const int32_t* pos_rows, const int32_t* pos_cols,
