@@ -499,10 +499,96 @@ static_assert(kFsMaxRpb == DG_TAB_MAX_ROW_SLOTS && DG_TAB_ROLE_PROJ_SLOTS_BITS =
 // 64-wide aggregate times the relation's W slab (seg_wave_proj's arithmetic).  LP = 8 (32-float
 // rows, plain sums only): eight pairs handed out at once, pair 8m + sub of a batch in lane
 // 8·sub + m — seg_gather<8>'s order, so a lane group adds the same pairs in the same order.
-template <bool PROJ, int U, int LP = 16>
+// OVL (the plain sums of gcn_tab_kernel): a batch's rounds overlapped, TabRing above.
+// A float4 read as a global_load (the pointer is known to address device memory), not the flat
+// load a pointer out of a descriptor gets.
+__device__ __forceinline__ float4 load4_global(const float* p) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    const v4f v = *(const v4f __attribute__((address_space(1)))*)(uintptr_t)p;
+    return make_float4(v.x, v.y, v.z, v.w);
+}
+
+// tab_wave's overlapped gather rounds over one batch of pairs (eoff, vbits: this lane's pair of
+// the batch, as handed out by the DPP row broadcasts).  The batch's steps go in chunks of kC, and
+// kD chunks' gathers are in flight before the first is folded: a wave of up to kC·kD·G pairs (24
+// at 64 floats, 48 at 32) waits one memory round trip, a longer one keeps kD - 1 chunks in flight
+// behind the chunk it folds.  Every gather of a chunk is issued, as a global load — a lane
+// without a pair reads the batch's pair 0 (lane 0's: a row this wave reads anyway) with weight
+// 0, adding the plain loop's 0 for every finite operand (a select on the loaded value instead
+// is common to both branches of run() and gets hoisted above them, with its wait) — so the
+// loads in flight are the same on every path, and each fold waits by count
+// (vmcnt(kC·(kD - 1)) in the steady state) instead of draining.  The weights are handed out again
+// at the fold, not kept: the stages are kC·kD float4, 24 VGPRs.  Chunk indices are template
+// constants, so the stages stay in registers.  The same pairs, weights and order of adds a lane
+// group as tab_wave's plain loop: the same bits.
+template <int LP>
+struct TabRing {
+    static constexpr int G = dg::kWave / LP, kC = 2, kD = 3, NC = (dg::kWave / G) / kC;
+    static_assert((dg::kWave / G) % kC == 0 && NC >= kD, "TabRing: chunks of a batch");
+    const float* xq;
+    int eoff, vbits, n, lane, safe;
+    float4 xv[kD][kC];
+
+    template <int M>
+    __device__ __forceinline__ int hand(int v) const {
+        if constexpr (LP == 16) {
+            return row_bcast<M>(v);
+        } else {  // a 16-lane row holds two lane groups' pairs: lanes 0-7 and 8-15
+            const int v0 = row_bcast<M>(v), v1 = row_bcast<8 + M>(v);
+            return ((lane >> 3) & 1) ? v1 : v0;
+        }
+    }
+    template <int M>
+    __device__ __forceinline__ bool has() const { return M * G + lane / LP < n; }
+    template <int C, int U = 0>
+    __device__ __forceinline__ void issue() {
+        if constexpr (U < kC) {
+            const int o = hand<C * kC + U>(eoff);
+            xv[C % kD][U] = load4_global(xq + (has<C * kC + U>() ? o : safe));
+            issue<C, U + 1>();
+        }
+    }
+    template <int C, int U = 0>
+    __device__ __forceinline__ void fold(float4& acc) const {
+        if constexpr (U < kC) {
+            const float w = __int_as_float(hand<C * kC + U>(vbits));
+            dg::fma4(acc, has<C * kC + U>() ? w : 0.f, xv[C % kD][U]);
+            fold<C, U + 1>(acc);
+        }
+    }
+    template <int C0, int C1>
+    __device__ __forceinline__ void fold_range(float4& acc) const {
+        if constexpr (C0 < C1) {
+            fold<C0>(acc);
+            fold_range<C0 + 1, C1>(acc);
+        }
+    }
+    // chunks max(0, J - (kD - 1)) .. J - 1 are in flight: issue chunk J if it has a pair and fold
+    // the oldest, else fold what is in flight, in order
+    template <int J>
+    __device__ __forceinline__ void run(float4& acc) {
+        constexpr int OLD = J >= kD - 1 ? J - (kD - 1) : 0;
+        if constexpr (J < NC) {
+            if (J * kC * G < n) {  // wave-uniform
+                issue<J>();
+                // (the folds below take acc from here, after the loads: without this the
+                // compiler hoists the fold both branches share above the branch — and so above
+                // the loads, which is the drained loop again)
+                asm volatile("" : "+v"(acc.x), "+v"(acc.y), "+v"(acc.z), "+v"(acc.w)::"memory");
+                if constexpr (J >= kD - 1) fold<OLD>(acc);
+                run<J + 1>(acc);
+                return;
+            }
+        }
+        fold_range<OLD, J>(acc);
+    }
+};
+
+template <bool PROJ, int U, int LP = 16, bool OVL = false>
 __device__ __forceinline__ float4 tab_wave(const dg_tab_desc& D, const uint2 first, const uint2* __restrict__ ovf,
                                            float4* ybuf, const int S) {
     static_assert(LP == 16 || (LP == 8 && !PROJ), "tab_wave: 64-float rows, or 32-float plain sums");
+    static_assert(!(OVL && PROJ), "tab_wave: overlapped rounds in the plain sums");
     constexpr int G = dg::kWave / LP;
     [[maybe_unused]] constexpr int kFsForm = 1;  // (profiling build: only the reassociated form stamps here)
     const int lane = threadIdx.x & 63;
@@ -527,12 +613,15 @@ __device__ __forceinline__ float4 tab_wave(const dg_tab_desc& D, const uint2 fir
             const int vbits = vb;
             vc = 0;
             vb = 0;
-            if (base + bsz < D.cnt) {
-                const uint2 q = nx[lane];
-                vc = (int)q.x;
-                vb = (int)q.y;
-                nx += 64;
-            }
+            const auto prefetch = [&]() {
+                if (base + bsz < D.cnt) {
+                    const uint2 q = nx[lane];
+                    vc = (int)q.x;
+                    vb = (int)q.y;
+                    nx += 64;
+                }
+            };
+            if constexpr (!OVL) prefetch();
             // DPP row broadcasts (the seg form's seg_gather): pair m·G + sub of the batch sits in
             // lane 16·sub + m.  Round 6: layer 2 (PROJ) too — since its W slice is read after the
             // gathers the unrolled broadcasts' registers fit (46 → 46 VGPRs), and its launch
@@ -540,34 +629,42 @@ __device__ __forceinline__ float4 tab_wave(const dg_tab_desc& D, const uint2 fir
             // per lane group: the same bits).
             constexpr int S = dg::kWave / G;
             static_assert(U >= 1 && U <= S && S % U == 0, "tab_wave: the unroll must divide the steps of a batch");
+            if constexpr (OVL) {
+                TabRing<LP> ring{xq, eoff, vbits, n, lane, __builtin_amdgcn_readfirstlane(eoff)};
+                ring.template issue<0>();
+                prefetch();  // (behind the first gathers: the wait the compiler puts at the head of
+                             // a batch, for loads it cannot see folded, then never waits for this one)
+                ring.template run<1>(acc);
+            } else {
 #pragma unroll
-            for (int it = 0; it < S / U; ++it) {
-                if (it * U * G >= n) break;  // wave-uniform
-                int o[U];
-                float w[U];
+                for (int it = 0; it < S / U; ++it) {
+                    if (it * U * G >= n) break;  // wave-uniform
+                    int o[U];
+                    float w[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int m = it * U + u;
-                    if constexpr (LP == 16) {
-                        o[u] = row_bcast_rt(eoff, m);
-                        w[u] = __int_as_float(row_bcast_rt(vbits, m));
-                    } else {  // a 16-lane row holds two lane groups' pairs: lanes 0-7 and 8-15
-                        const bool odd = (lane >> 3) & 1;
-                        const int o0 = row_bcast_rt(eoff, m), o1 = row_bcast_rt(eoff, 8 + m);
-                        const int w0 = row_bcast_rt(vbits, m), w1 = row_bcast_rt(vbits, 8 + m);
-                        o[u] = odd ? o1 : o0;
-                        w[u] = __int_as_float(odd ? w1 : w0);
+                    for (int u = 0; u < U; ++u) {
+                        const int m = it * U + u;
+                        if constexpr (LP == 16) {
+                            o[u] = row_bcast_rt(eoff, m);
+                            w[u] = __int_as_float(row_bcast_rt(vbits, m));
+                        } else {  // a 16-lane row holds two lane groups' pairs: lanes 0-7 and 8-15
+                            const bool odd = (lane >> 3) & 1;
+                            const int o0 = row_bcast_rt(eoff, m), o1 = row_bcast_rt(eoff, 8 + m);
+                            const int w0 = row_bcast_rt(vbits, m), w1 = row_bcast_rt(vbits, 8 + m);
+                            o[u] = odd ? o1 : o0;
+                            w[u] = __int_as_float(odd ? w1 : w0);
+                        }
                     }
-                }
-                float4 xv[U];
+                    float4 xv[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const bool ok = (it * U + u) * G + sub < n;
-                    xv[u] = ok ? *reinterpret_cast<const float4*>(xq + o[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (!ok) w[u] = 0.f;
-                }
+                    for (int u = 0; u < U; ++u) {
+                        const bool ok = (it * U + u) * G + sub < n;
+                        xv[u] = ok ? *reinterpret_cast<const float4*>(xq + o[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        if (!ok) w[u] = 0.f;
+                    }
 #pragma unroll
-                for (int u = 0; u < U; ++u) dg::fma4(acc, w[u], xv[u]);
+                    for (int u = 0; u < U; ++u) dg::fma4(acc, w[u], xv[u]);
+                }
             }
         }
         acc = dg::xor_sum4_from<LP>(acc);
@@ -639,9 +736,27 @@ __device__ __forceinline__ void add_lane_sets(float4& tot, const float4& v, int 
 // 4.29-4.34 µs; scripts/variants/serial_lds_sum.py kept the A/B.)
 template <int W>
 __device__ __forceinline__ float4 lds_ordered_sum(const float4 (*rows)[W], int K, int q) {
+    // Up to 16 rows (a group of a weighted table): the reads of four rows, then of two, are issued
+    // together ahead of their adds — runs of whole rows only, nothing predicated — so the sum
+    // waits K/4 + 2 LDS round trips at most instead of K - 1.  The adds and their order are the
+    // loop's of one read an add.
     float4 s = rows[0][q];
+    int u = 1;
 #pragma unroll 1
-    for (int u = 1; u < K; ++u) dg::add4(s, rows[u][q]);
+    for (; u + 4 <= K; u += 4) {
+        const float4 a = rows[u][q], b = rows[u + 1][q], c = rows[u + 2][q], d = rows[u + 3][q];
+        dg::add4(s, a);
+        dg::add4(s, b);
+        dg::add4(s, c);
+        dg::add4(s, d);
+    }
+    if (u + 2 <= K) {
+        const float4 a = rows[u][q], b = rows[u + 1][q];
+        dg::add4(s, a);
+        dg::add4(s, b);
+        u += 2;
+    }
+    if (u < K) dg::add4(s, rows[u][q]);
     return s;
 }
 
@@ -660,14 +775,6 @@ __device__ __forceinline__ uint32_t slot_lane_offset(int lane, int S) {
 // flagged finishing wave's Q row).
 __device__ __forceinline__ float4* tab_aux_row(const dg_tab_desc& D) {
     return reinterpret_cast<float4*>(((uint64_t)(uint32_t)D.aux_hi << 32) | (uint32_t)D.aux_lo);
-}
-
-// A float4 read as a global_load (the pointer is known to address device memory), not the flat
-// load a pointer out of a descriptor gets.
-__device__ __forceinline__ float4 load4_global(const float* p) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    const v4f v = *(const v4f __attribute__((address_space(1)))*)(uintptr_t)p;
-    return make_float4(v.x, v.y, v.z, v.w);
 }
 
 // PEER (dg_gcn_fused_tab_peer_f32): each finished row also goes to every peer's copy of its
@@ -733,7 +840,7 @@ __global__ __launch_bounds__(64 * NW) void gcn_tab_kernel(const uint2* __restric
     DG_FS_STAMP(1);  // descriptor and first pairs in registers
     if constexpr (!PROJ) DG_FS_STAMP(2);  // (layer 2: stamp 2 marks its gathers done, in tab_wave)
     const int ms = lane >> 3;
-    const float4 res = tab_wave<PROJ, PROJ ? kTabUP : kTabU, LP>(D, first, ovf, ybuf[wave], S);
+    const float4 res = tab_wave<PROJ, PROJ ? kTabUP : kTabU, LP, !PROJ>(D, first, ovf, ybuf[wave], S);
     // DEC: this lane's slice of the decoder's parameters — rows 4(l>>3) .. +4 of G at output float4
     // l & 7, and l at both — issued here as POST's W slice is, by the flagged finishing waves only
     // (48 VGPRs as the plain instance; issued before the gather loop instead: 66 VGPRs and the same

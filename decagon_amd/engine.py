@@ -110,6 +110,18 @@ L2_PREPROJECT = knob("DG_L2_PREPROJECT", True)
 # ... one wave projecting every row of its workgroup onto a relation (the W slab read once a
 # workgroup: config S's layer 1 5.46 -> 5.31 us); 0: one (row, relation) a wave
 L2_PREPROJECT_SHARE = knob("DG_L2_PREPROJECT_SHARE", True)
+# ... with a launch's wave slots dealt in proportion to pairs (PreparedFusedTab weighted): a wave
+# for every T pairs of a row's group in 16-slot workgroups, rows packed while their slots fit,
+# instead of an equal share of the workgroup a row — a wave then runs one gather round (at most T
+# pairs) whatever its row's length.  Only where _tab_balance holds (TAB_BALANCE = 0 keeps the
+# per-relation tables); 0: the equal-share tables in both layers
+TAB_WEIGHTED = knob("DG_TAB_WEIGHTED", 1)
+# ... T per layer, 0 = that layer keeps its equal shares.  Layer 2 (32 floats a row): 48, one
+# overlapped round of the gather ring — config S's step 13.22-13.29 -> 12.85-13.04 us, against
+# 13.09 at 64 and 13.80-13.99 at 32 with layer 1 at 24.  Layer 1 (64 floats): off — weighted at
+# 16 / 20 / 24 / 32 it measured slower than its equal shares at every T (24: +0.35 us), DESIGN §5
+TAB_WEIGHTED_T64 = knob("DG_TAB_WEIGHTED_T64", 0)
+TAB_WEIGHTED_T32 = knob("DG_TAB_WEIGHTED_T32", 48)
 # ... and layer 2's launch in turn makes the DEDICOM decoder's row operands
 # Q[r] = l ∘ ((E[r] ∘ l)·G) from the embedding rows it finishes (dg_gcn_fused_tab_dec_f32), for a
 # decoder that attaches (ForwardPlan.attach_decoder_rows; kernels.PreparedDecoderHinge does): a
@@ -332,6 +344,14 @@ def snake_bins(costs: Sequence[float], bin_size: int, max_swaps: int = 4000) -> 
 def _tab_balance(d_in: int, d_out: int) -> bool:
     """TAB_BALANCE's choice for a wave-table fused launch (layer 1: d_in == d_out)."""
     return TAB_BALANCE >= 2 or (TAB_BALANCE == 1 and d_in == d_out)
+
+
+def _tab_weighted(d_in: int, d_out: int) -> int:
+    """TAB_WEIGHTED's T for a launch of the pre-projected plan (plain sums, d_in == d_out): 0 =
+    the equal-share table."""
+    if not (TAB_WEIGHTED and d_in == d_out and _tab_balance(d_in, d_out)):
+        return 0
+    return max(0, TAB_WEIGHTED_T64 if d_in == 64 else TAB_WEIGHTED_T32)  # (T = 0: this layer's equal shares)
 
 
 def _tab_groups_fit(tgts, d: int) -> bool:
@@ -842,8 +862,8 @@ class ForwardPlan:
     def _preproject_fits(self, keep_sums: bool) -> bool:
         """L2_PREPROJECT's conditions: a one-GPU forward-only plan whose layers run the wave-table
         fused form, with a wave slot in layer 1's workgroups for every (row, sourced relation)."""
-        if not (L2_PREPROJECT and self.fused_seg and WAVE_TABLE and not keep_sums and self.drop_state is None
-                and self.shard is None):
+        self.tab_weighted = False
+        if not (self.fused_seg and WAVE_TABLE and not keep_sums and self.drop_state is None and self.shard is None):
             return False
         order = list(self.targets)
         if any(et[1] not in self.targets for et in self.edge_types):
@@ -853,7 +873,13 @@ class ForwardPlan:
         rels = {et: self.g.groups[et].n_rels for et in self.edge_types}
         waves_t = [sum(rels[et] for et in self.targets[i]) for i in order]
         sourced_t = [sum(k for et, k in rels.items() if et[1] == i) for i in order]
-        return wavetable.tab_proj_fit(waves_t, sourced_t, _tab_balance(self.h1, self.h1), L2_PREPROJECT_SHARE)
+        if not wavetable.tab_proj_fit(waves_t, sourced_t, _tab_balance(self.h1, self.h1), L2_PREPROJECT_SHARE):
+            return False
+        # TAB_WEIGHTED: where a weighted workgroup also has the wave slots for a row's jobs.  (Read
+        # by layer 1 with L2_PREPROJECT = 0 too: the plan's A/B fallback keeps layer 1's table, a
+        # row's waves and so H1's bits, and differs in layer 2 alone.)
+        self.tab_weighted = wavetable.weighted_proj_fit(sourced_t, L2_PREPROJECT_SHARE)
+        return bool(L2_PREPROJECT)
 
     def _spec(self, et, x: torch.Tensor, out, d) -> kernels.RelGroupSpec:
         grp = self.g.groups[et]
@@ -928,12 +954,15 @@ class ForwardPlan:
                     pj.append(kernels.TabProjSpec(fused_t.index(et[1]), W2, self.proj[et], grp.n_rels,
                                                   None if grp.rel_map is None else grp.rel_map.cpu().numpy()))
                 launches.append(kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d), projs=pj,
-                                                         share_proj=L2_PREPROJECT_SHARE))
+                                                         share_proj=L2_PREPROJECT_SHARE,
+                                                         weighted=_tab_weighted(d_in, d) if self.tab_weighted else 0))
             elif WAVE_TABLE and self.preproj and d_in == d == 32 and _tab_groups_fit(tgts, d):
                 # layer 2 over the P stacks layer 1 made: layer 1's shape at half the width
-                launches.append(kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d)))
+                weighted = _tab_weighted(d_in, d) if self.tab_weighted else 0
+                launches.append(kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d),
+                                                         weighted=weighted))
                 # (attach_decoder_rows rebuilds this launch with the decoder's row operands)
-                self._l2_tab = (tgts, d_in, d, _tab_balance(d_in, d), list(fused_t), launches[-1])
+                self._l2_tab = (tgts, d_in, d, _tab_balance(d_in, d), list(fused_t), launches[-1], weighted)
             else:
                 launches.append(kernels.PreparedFusedSeg(tgts, d_in, d))
             self.launch_groups[id(launches[-1])] = [et for i in fused_t for et in self.targets[i]]
@@ -1235,10 +1264,10 @@ class ForwardPlan:
                 return None
             self._dec["users"] += 1
             return self._dec["Q"]
-        tgts, d_in, d, balance, fused_t, plain = tab
+        tgts, d_in, d, balance, fused_t, plain, weighted = tab
         E = self.embeddings[node_type]
         Q = torch.zeros((E.shape[0], 32), dtype=torch.float32, device=E.device)
-        launch = kernels.PreparedFusedTab(tgts, d_in, d, balance=balance,
+        launch = kernels.PreparedFusedTab(tgts, d_in, d, balance=balance, weighted=weighted,
                                           dec=kernels.TabDecSpec(fused_t.index(node_type), G, l, Q))
         self._swap_l2(plain, launch)
         self._dec = {"key": key, "Q": Q, "G": G, "l": l, "launch": launch, "users": 1, "runs": self.runs}

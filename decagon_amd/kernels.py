@@ -348,6 +348,7 @@ def _upload_table(owner, tab: wavetable.HostTable, dev) -> "_lib.DgWaveTable":
     owner._pairs = torch.from_numpy(tab.pairs).to(dev)
     owner._ovf = torch.from_numpy(tab.ovf).to(dev)
     owner.n_blocks, owner.nw, owner.slot_pairs = tab.n_blocks, tab.nw, tab.slot_pairs
+    owner.host_plan = list(tab.plan)  # per workgroup, as the builder documents
     raw = torch.from_numpy(tab.desc.view(np.uint8).copy())
     owner._desc = torch.empty(raw.numel() + 64, dtype=torch.uint8, device=dev)
     off = (-owner._desc.data_ptr()) % 64
@@ -407,10 +408,16 @@ class PreparedFusedTab(PreparedFusedSeg):
     group's waves, waves given to groups by their pairs; the reassociated layer 2 keeps one
     relation per wave (its W slab) and gives the spare slots to the longest segments.  The kernel
     and its finishing roles are unchanged — a group's normalising wave sums its waves' rows in
-    order — so only the fp32 summation order within a group differs from the per-relation form."""
+    order — so only the fp32 summation order within a group differs from the per-relation form.
+
+    weighted = T > 0 (with balance; plain sums, d_in == d_out, no peer): wave slots in proportion
+    to pairs — a wave for every T pairs of a row's group in 16-slot workgroups, rows packed while
+    their slots fit (wavetable.fused_table) — so that a wave runs one gather round whatever its
+    row's length.  The same kernel and roles again: only the summation order within a group differs."""
 
     def __init__(self, targets, d_in: int, d_out: int, peer=None, balance: bool = False,
-                 projs: Sequence[TabProjSpec] = (), share_proj: bool = True, dec: Optional[TabDecSpec] = None):
+                 projs: Sequence[TabProjSpec] = (), share_proj: bool = True, dec: Optional[TabDecSpec] = None,
+                 weighted: int = 0):
         super().__init__(targets, d_in, d_out, peer=peer)
         specs = self._keep[0]
         narrow = d_in == d_out == 32 and all(s.w is None for s in specs) and peer is None
@@ -443,7 +450,7 @@ class PreparedFusedTab(PreparedFusedSeg):
             if (tuple(pj.w.shape[1:]) != (64, 32) or tuple(pj.out.shape) != (K, rows, 32) or len(slabs) != pj.n_rels
                     or any(not 0 <= x < K for x in slabs) or pj.out.data_ptr() % 16 or pj.w.data_ptr() % 16):
                 raise ValueError("projection jobs: w [K, 64, 32], P [K, target rows, 32], slabs inside both")
-        self.balance = balance
+        self.balance, self.weighted = balance, weighted
         data = {id(s): _seg_data(s) for s in specs}
         self._tab = _upload_table(self, wavetable.fused_table(
             [(out.data_ptr(), n_rows, [data[id(s)] for s in gs], relu) for out, n_rows, gs, relu in targets],
@@ -451,7 +458,7 @@ class PreparedFusedTab(PreparedFusedSeg):
             projs=[wavetable.ProjData(pj.target, pj.w.data_ptr(), pj.out.data_ptr(), pj.n_rels, pj.slab)
                    for pj in self.projs],
             share_proj=share_proj, dec=None if dec is None else wavetable.DecData(dec.target, dec.out.data_ptr()),
-            peer=peer is not None, slot=knob("DG_TAB_SLOT", 0)), specs[0].x.device)
+            peer=peer is not None, slot=knob("DG_TAB_SLOT", 0), weighted=weighted), specs[0].x.device)
         if dec is not None:
             self._keep = self._keep + (dec,)
             self._tfn, self._tname = _lib.load().dg_gcn_fused_tab_dec_f32, "dg_gcn_fused_tab_dec_f32"

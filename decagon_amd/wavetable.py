@@ -327,6 +327,78 @@ def tab_proj_fit(waves_t: Sequence[int], sourced_t: Sequence[int], balance: bool
     return all(_proj_jobs([True] * rpb, k, nw, share) is not None for rpb, k in zip(rpbs, sourced_t))
 
 
+WEIGHTED_STRIDE = 16               # wave slots of a workgroup of a weighted table
+
+
+def _weighted_slots(sizes: Sequence[int], T: int) -> int:
+    """Wave slots of one row of a weighted table: a wave for every T pairs of each group (at
+    least one a group), capped at the workgroup's WEIGHTED_STRIDE — a row past the cap has waves
+    of more than T pairs."""
+    if len(sizes) > WEIGHTED_STRIDE:
+        raise ValueError(f"{len(sizes)} groups for {WEIGHTED_STRIDE} wave slots")
+    return min(max(sum(max(1, -(-int(n) // T)) for n in sizes), len(sizes)), WEIGHTED_STRIDE)
+
+
+def _weighted_max_rows(n_rels: int, share: bool) -> int:
+    """Rows a workgroup of a weighted table may hold when each is projected onto n_rels relations:
+    the most (up to DG_TAB_MAX_ROW_SLOTS) whose jobs (_proj_jobs_paired) fit its wave slots; 0 =
+    not even one row's."""
+    for rows in range(DG_TAB_MAX_ROW_SLOTS, 0, -1):
+        if (-(-rows // 2) if share else rows) * n_rels <= WEIGHTED_STRIDE:
+            return rows
+    return 0
+
+
+def _proj_jobs_paired(rows_present: Sequence[bool], n_rels: int, nw: int, share: bool = True):
+    """_proj_jobs for a workgroup of up to DG_TAB_MAX_ROW_SLOTS rows in which no wave projects
+    more than two: with `share`, row slots (0, 1) and (2, 3) each share a wave per relation (a
+    slot without a row is left out, a pair without rows has no job); without, a wave per (row,
+    relation).  Same filling order as _proj_jobs; None when the jobs of a full workgroup exceed nw."""
+    rpb = len(rows_present)
+    if not share:
+        return _proj_jobs(rows_present, n_rels, nw, False)
+    if -(-rpb // 2) * n_rels > nw:
+        return None
+    jobs: List[Optional[Tuple[Tuple[int, ...], int]]] = [None] * nw
+    order = list(range(rpb, nw)) + list(range(min(rpb, nw)))
+    todo = []
+    for s0 in range(0, rpb, 2):
+        present = tuple(s for s in range(s0, min(s0 + 2, rpb)) if rows_present[s])
+        if present:
+            todo += [(present, k) for k in range(n_rels)]
+    for w, job in zip(order, todo):
+        jobs[w] = job
+    return jobs
+
+
+def weighted_proj_fit(sourced_t: Sequence[int], share: bool = True) -> bool:
+    """tab_proj_fit for a weighted table: every target's workgroups can hold at least one row with
+    a wave slot for each of its projection jobs."""
+    return all(_weighted_max_rows(k, share) >= 1 for k in sourced_t)
+
+
+def _weighted_plan(tb: "_WaveTable", targets, g_first, T: int, max_rows: Sequence[int]):
+    """(plan, first wave slot of each row of each workgroup) of a weighted table: consecutive rows
+    of one target packed in order into a workgroup while their wave slots (_weighted_slots) sum to
+    at most WEIGHTED_STRIDE and they are at most max_rows[target]."""
+    plan, firsts = [], []
+    for t, (_, n_rows, gspecs, _) in enumerate(targets):
+        gs = [int(g_first[t]) + gl for gl in range(len(gspecs))]
+        r0, cur = 0, []
+        for r in range(n_rows):
+            w = _weighted_slots([sum(tb.seg_len(g, k, r) for k in range(s.n_rels)) for g, s in zip(gs, gspecs)], T)
+            if cur and (sum(cur) + w > WEIGHTED_STRIDE or len(cur) >= max_rows[t]):
+                plan.append((t, r0, len(cur)))
+                firsts.append(cur)
+                r0, cur = r, []
+            cur.append(w)
+        if cur:
+            plan.append((t, r0, len(cur)))
+            firsts.append(cur)
+    # per workgroup, per row: (first wave slot, wave slots)
+    return plan, [[(sum(c[:i]), c[i]) for i in range(len(c))] for c in firsts]
+
+
 def _split_even(n: int, parts: int) -> List[Tuple[int, int]]:
     """[a, b) slices of n items over `parts` waves, the first n % parts one longer."""
     q, rem = divmod(n, parts)
@@ -396,7 +468,7 @@ def _mark_dec_rows(desc: np.ndarray, plan, stride: int, target: int, n_rows: int
 
 def fused_table(targets, d_in: int, d_out: int, balance: bool = False, projs: Sequence[ProjData] = (),
                 share_proj: bool = True, dec: Optional[DecData] = None, peer: bool = False,
-                slot: int = 0) -> HostTable:
+                slot: int = 0, weighted: int = 0) -> HostTable:
     """The table of a dg_gcn_fused_tab_*_f32 launch.  targets = [(out address, n_rows, [SegData],
     relu)]; a workgroup finishes rows-per-workgroup consecutive rows of one target
     (HostTable.plan: (target, first row, rows per workgroup) per workgroup).  balance: each row's
@@ -405,6 +477,10 @@ def fused_table(targets, d_in: int, d_out: int, balance: bool = False, projs: Se
     finishing waves of one target's rows also store the decoder's row operand.  peer: the table of
     the exchange form (the auxiliary words of a finishing wave are the same in every table without
     jobs; the exchange needs at least one workgroup).  slot: a fixed slot_pairs, 0 = by cover.
+    weighted = T > 0 (a balanced table of plain sums, d_in == d_out, without an exchange): wave
+    slots in proportion to pairs instead of an equal share a row — workgroups of WEIGHTED_STRIDE
+    slots, a row taking _weighted_slots of them (a wave for every T pairs of a group), rows packed
+    in order (_weighted_plan), projection jobs at most two rows a wave (_proj_jobs_paired).
 
     The auxiliary words (aux_lo, aux_hi) of a wave hold, in this order of precedence: its
     projection job's first P row address; its decoder row's address; on any other finishing
@@ -412,13 +488,25 @@ def fused_table(targets, d_in: int, d_out: int, balance: bool = False, projs: Se
     specs = [s for _, _, gs, _ in targets for s in gs]
     proj = d_out != d_in
     waves_t = [sum(s.n_rels for s in gs) for _, _, gs, _ in targets]
-    nw, stride, rpbs = _tab_geometry(waves_t, balance)
-    plan = []
-    for t, (_, n_rows, _, _) in enumerate(targets):
-        plan += [(t, r0, rpbs[t]) for r0 in range(0, n_rows, rpbs[t])]
+    g_first = np.cumsum([0] + [len(gs) for _, _, gs, _ in targets])
+    row_slots = None  # weighted: per workgroup, per row, (first wave slot, wave slots)
+    if weighted:
+        if weighted < 1 or not balance or proj or peer:
+            raise ValueError("a weighted table: balanced plain sums (d_in == d_out) without an exchange, T >= 1")
+        nw = stride = WEIGHTED_STRIDE
+        max_rows = [_weighted_max_rows(sum(pj.n_rels for pj in projs if pj.target == t), share_proj)
+                    for t in range(len(targets))]
+        if not all(max_rows):
+            raise ValueError(f"one row's projection jobs for {nw} wave slots")
+        plan, row_slots = _weighted_plan(_WaveTable(specs, 0, proj, lp=d_in // 4), targets, g_first, weighted,
+                                         max_rows)
+    else:
+        nw, stride, rpbs = _tab_geometry(waves_t, balance)
+        plan = []
+        for t, (_, n_rows, _, _) in enumerate(targets):
+            plan += [(t, r0, rpbs[t]) for r0 in range(0, n_rows, rpbs[t])]
     tb = _WaveTable(specs, len(plan) * stride, proj, lp=d_in // 4)
     d = tb.desc
-    g_first = np.cumsum([0] + [len(gs) for _, _, gs, _ in targets])
     for b, (t, r0, rpb) in enumerate(plan):
         out, n_rows, gspecs, relu = targets[t]
         gc = len(gspecs)
@@ -429,11 +517,14 @@ def fused_table(targets, d_in: int, d_out: int, balance: bool = False, projs: Se
             r = r0 + slot_r
             if r >= n_rows:
                 continue
+            first = slot_r * per_row
+            if row_slots is not None:
+                first, per_row = row_slots[b][slot_r]
             if balance:
                 waves = _balanced_waves(tb, gs, nr, r, per_row, proj)
             else:  # one wave per relation, groups in order
                 waves = [[[(k, 0, tb.seg_len(gs[gl], k, r))] for k in range(nr[gl])] for gl in range(gc)]
-            w = slot_r * per_row
+            w = first
             for gl, wg in enumerate(waves):
                 for pieces in wg:
                     tb.wave(b * stride + w, gs[gl], r, pieces)
@@ -444,12 +535,13 @@ def fused_table(targets, d_in: int, d_out: int, balance: bool = False, projs: Se
             d["wr"][i] = encode_wr(gc, relu, slot_r)
             d["aux_lo"][i], d["aux_hi"][i] = r * d_out * 4, n_rows * d_out * 4
             d["gwaves"][i] = encode_gwaves([len(wg) for wg in waves])
-            d["first_wave"][i] = slot_r * per_row
+            d["first_wave"][i] = first
         # projection jobs: W2_k in `w`, the address of row slot 0's P row in the auxiliary words
         # (a projecting launch has no exchange)
         rels = [(pj, k) for pj in projs if pj.target == t for k in range(pj.n_rels)]
         if rels:
-            jobs = _proj_jobs([r0 + s < n_rows for s in range(rpb)], len(rels), nw, share_proj)
+            jobs = (_proj_jobs_paired if weighted else _proj_jobs)([r0 + s < n_rows for s in range(rpb)], len(rels),
+                                                                   nw, share_proj)
             if jobs is None:
                 raise ValueError(f"{rpb} rows x {len(rels)} projection jobs for {nw} wave slots")
             for w, job in enumerate(jobs):
