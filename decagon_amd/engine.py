@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import heapq
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -30,6 +30,7 @@ import torch
 
 from . import kernels, wavetable
 from ._lib import DG_EPI_L2NORM, DG_EPI_RELU, DG_MAX_GROUPS
+from .peer import SLOT_FUSED, SLOT_KERNEL, SLOT_PROBE, PeerExchange, device_tensor
 from .sparse import HostCSR, MergedCSR, chunk_segments, merge_chunks, merge_windows, staged_layout
 from .tuning import knob
 
@@ -72,11 +73,6 @@ N_WINDOWS = knob("DG_WINDOWS", 2)
 # node types with at most this many rows finish in the fused row-per-workgroup kernel; larger
 # ones run partial mode + epilogue (one wave per row keeps more gathers in flight)
 FUSED_MAX_ROWS = knob("DG_FUSED_MAX_ROWS", 4096)
-# a layer's gather-bound launch beside its LDS-bound staged launch on a second stream: no gain
-# measured (config P step 494.8 us concurrent vs 496.5 sequential; the staged kernel slows by
-# what the other saves) and the fork / join cost ~10 us of idle GPU each at small per-rank
-# shares (8-GPU rehearsal), so one stream by default
-CONCURRENT_LAUNCHES = knob("DG_CONCURRENT", False)
 # layer 2 of staged groups makes its slabs H1_j·W2_k on the MFMA inside the SpMM kernel
 STAGED_PROJ = knob("DG_STAGED_PROJ", True)
 # one-GPU plans whose node types all fit dg_gcn_fused_seg_f32 (config S) use it, layer 2
@@ -126,19 +122,10 @@ TAB_WEIGHTED_T32 = knob("DG_TAB_WEIGHTED_T32", 48)
 # Q[r] = l ∘ ((E[r] ∘ l)·G) from the embedding rows it finishes (dg_gcn_fused_tab_dec_f32), for a
 # decoder that attaches (ForwardPlan.attach_decoder_rows; kernels.PreparedDecoderHinge does): a
 # score is then a 32-float dot product.  Read per attachment: DG_DEC_PREPROJECT=0 never attaches.
-STAGED_FIRST = knob("DG_STAGED_FIRST", True)
 # sharded forward plans: layer 2 of the non-staged groups reassociated over the rank's own rows
 # and relations, Σ_k (Â_k·H1_j)·W2_k in dg_spmm_seg_f32, instead of every rank projecting all of
 # H1_j·W2_k (config P's PPI: 19,085 rows x 2 relations, 9.4 µs on every rank at N = 8)
 REASSOC_ROWS = knob("DG_REASSOC_ROWS", True)
-# sharded forward plans: layer 1 of the row-split, non-windowed, non-staged groups in
-# dg_spmm_seg_f32 (one wave per (row, relation), its segment's pairs in one load) instead of
-# dg_spmm_groups_f32 (one wave per two (chunk, row) items): a rank's short row block (config P
-# at N = 8: 2,386 protein rows, the PPI's two relations in one chunk) keeps more waves in flight.
-# Off: at P's N = 8 share it took 3-5 us off seven ranks (107.1-108.0 -> 102.7-104.1 us) but
-# added 1.7 us to the slowest (rank 4, 110.6 -> 112.3: a wave per (row, relation) walks a hub
-# row's long segment alone), so the max over ranks got worse
-SEG_ROWS_L1 = knob("DG_SEG_ROWS_L1", False)
 
 
 def _epilogue(targets, d: int, flags: int, peer=None, push=None):
@@ -354,10 +341,11 @@ def _tab_weighted(d_in: int, d_out: int) -> int:
     return max(0, TAB_WEIGHTED_T64 if d_in == 64 else TAB_WEIGHTED_T32)  # (T = 0: this layer's equal shares)
 
 
-def _tab_groups_fit(tgts, d: int) -> bool:
+def _tab_groups_fit(n_groups: Sequence[int], d: int) -> bool:
     """The wave-table fused form finishes a row in one wave, one lane set of d/4 lanes per group
-    (PreparedFusedTab): at most 64 / (d/4) groups a target; otherwise the fused-seg form."""
-    return all(len(gs) <= 64 // (d // 4) for _, _, gs, _ in tgts)
+    (PreparedFusedTab): at most 64 / (d/4) groups a target (n_groups: each target's count);
+    otherwise the fused-seg form."""
+    return all(k <= 64 // (d // 4) for k in n_groups)
 
 
 def choose_chunk(n_rels: int, n_rows: int, nnz: int, d: int, target_waves: int = 32768) -> int:
@@ -538,6 +526,240 @@ class LayerWeights:
     stacks: Dict[EdgeType, torch.Tensor]
 
 
+@dataclass
+class LayerForms:
+    """The launch form of one layer of a plan (decide_forms)."""
+
+    layer: int  # 1 or 2: the width, relu, outputs, padded buffers and peer slots follow from it
+    d: int      # output width
+    d_in: int   # operand width of its seg launches: h1 where layer 2 is reassociated, else d
+    # "seg_rows": one launch finishes this rank's row block of every node type (seg mode);
+    # "fused_seg": the one-GPU fused-seg / wave-table launch; "fused": dg_gcn_fused_f32 over
+    # plan.fused, the other node types partial; "partial": SpMM launches and a finishing step
+    kind: str = "partial"
+    # seg_rows / fused_seg: "tab" the wave-table form, "narrow" its 32 -> 32 form over the P
+    # stacks layer 1 made, "" dg_gcn_fused_seg_f32
+    table: str = ""
+    peer_red: bool = False  # the pushing epilogue launch carries the peer all-reduce
+
+    @property
+    def relu(self) -> bool:
+        return self.layer == 1
+
+
+@dataclass
+class PlanForms:
+    """Every launch-form decision of one ForwardPlan (decide_forms); the plan mirrors the
+    fields of FORM_ATTRS as attributes of the same names."""
+
+    flat_mode: bool = False
+    sums_mode: bool = False  # partial mode whose epilogue also writes each S_ij
+    seg_mode: bool = False
+    fused_seg: bool = False
+    peer_reduce: bool = False
+    tab_weighted: bool = False
+    fused: List[int] = field(default_factory=list)
+    staged_proj: set = field(default_factory=set)
+    preproj: set = field(default_factory=set)
+    seg_proj: set = field(default_factory=set)
+    proj_fused: List[EdgeType] = field(default_factory=list)  # projected by the launch finishing H1_j
+    peer_fit: bool = True  # the peer all-reduce's targets fit ONE epilogue launch (_peer_reduce_fits)
+    layers: Dict[int, LayerForms] = field(default_factory=dict)
+
+
+FORM_ATTRS = ("flat_mode", "sums_mode", "seg_mode", "fused_seg", "peer_reduce", "tab_weighted", "fused",
+              "staged_proj", "preproj", "seg_proj")
+
+
+def _targets(dgraph: DeviceGraph) -> Dict[int, List[EdgeType]]:
+    """Node type -> the edge types into it, in the graph's order."""
+    targets: Dict[int, List[EdgeType]] = {}
+    for et in dgraph.edge_types:
+        targets.setdefault(et[0], []).append(et)
+    if any(len(v) > DG_MAX_GROUPS for v in targets.values()):
+        raise ValueError(f"more than {DG_MAX_GROUPS} edge types into one node type")
+    return targets
+
+
+def _local_rows(dgraph: DeviceGraph, i: int) -> int:
+    """Rows of node type i this rank finishes (a row-split rank: its block)."""
+    if i in dgraph.row_block:
+        return dgraph.row_block[i][1] - dgraph.row_block[i][0]
+    return dgraph.n_nodes[i]
+
+
+def _fused_targets(dgraph: DeviceGraph, targets, sharded: bool, keep_sums: bool, fused_rows: bool) -> List[int]:
+    """Node types one dg_gcn_fused_f32 launch finishes: at most FUSED_MAX_ROWS (local) rows,
+    every group one chunk (and not staged).  Sharded plans finish only row-split node types
+    this way, when the shard asks for it (`fused_rows`: their rows are complete on this
+    rank; relation-sharded ones need the all-reduce first), and the sharded backward takes
+    none."""
+    row_block, groups = dgraph.row_block, dgraph.groups
+    if sharded and (keep_sums or not row_block or not fused_rows):
+        return []
+    return [i for i, ets in targets.items()
+            if (not sharded or i in row_block)
+            and 0 < _local_rows(dgraph, i) <= FUSED_MAX_ROWS
+            and all(groups[et].n_chunks == 1 and groups[et].n_rels > 0 and not groups[et].staged for et in ets)]
+
+
+def _preproject_fit(targets, rels: Dict[EdgeType, int], h1: int) -> Tuple[bool, bool]:
+    """(Layer 1's wave-table workgroups have a wave slot for every (row, sourced relation):
+    L2_PREPROJECT can hold; so have TAB_WEIGHTED's weighted workgroups for a row's jobs)."""
+    order = list(targets)
+    if any(et[1] not in targets for et in rels):
+        return False, False
+    if not _tab_groups_fit([len(targets[i]) for i in order], h1):  # (layer 2's 32-wide bound is the looser)
+        return False, False
+    waves_t = [sum(rels[et] for et in targets[i]) for i in order]
+    sourced_t = [sum(k for et, k in rels.items() if et[1] == i) for i in order]
+    if not wavetable.tab_proj_fit(waves_t, sourced_t, _tab_balance(h1, h1), L2_PREPROJECT_SHARE):
+        return False, False
+    return True, wavetable.weighted_proj_fit(sourced_t, L2_PREPROJECT_SHARE)
+
+
+def _epilogue_fits(n_targets: int, n_groups: int) -> bool:
+    """Whether ONE epilogue launch takes these targets (dg_gcn_epilogue_multi_f32 / _peer_f32)."""
+    return n_targets <= 8 and n_groups <= DG_MAX_GROUPS
+
+
+def _peer_reduce_fits(dgraph: DeviceGraph, targets) -> bool:
+    """Whether the pushing epilogue launch can carry the peer all-reduce: the row-split node
+    types plus every relation-sharded node type with local relations as targets of ONE
+    dg_gcn_epilogue_peer_f32 launch.  A larger graph keeps the flat buffer and the RCCL
+    all-reduce instead (it used to raise)."""
+    t = [i for i in targets if i in dgraph.row_block]
+    t += [i for i in targets if i not in dgraph.row_block and any(dgraph.groups[et].n_rels for et in targets[i])]
+    return _epilogue_fits(len(t), sum(len(targets[i]) for i in t))
+
+
+def _layer_forms(f: PlanForms, dgraph: DeviceGraph, layer: int, h1: int, h2: int) -> LayerForms:
+    """One layer's launch form under the plan-wide forms f."""
+    targets = _targets(dgraph)
+    d = h1 if layer == 1 else h2
+    reassoc = layer == 2 and bool(f.seg_proj)
+    lf = LayerForms(layer, d, h1 if reassoc else d)
+    row_rels = [sum(dgraph.groups[et].n_rels for et in ets) for ets in targets.values()]
+    if f.seg_mode and SEG_FUSED and all(r <= SEG_FUSED_MAX_ITEMS for r in row_rels):
+        lf.kind = "seg_rows"
+    elif f.fused_seg:
+        lf.kind = "fused_seg"
+    elif f.fused:
+        lf.kind = "fused"
+    if lf.kind in ("seg_rows", "fused_seg") and WAVE_TABLE and _tab_groups_fit([len(v) for v in targets.values()], d):
+        if lf.d_in == 64 and (d == 64 or reassoc):
+            lf.table = "tab"
+        elif lf.kind == "fused_seg" and f.preproj and lf.d_in == d == 32:
+            lf.table = "narrow"
+    # the peer all-reduce rides where the layer has both relation-sharded sums and a pushing
+    # epilogue over row-split blocks
+    split_t = [i for i in targets if i in dgraph.row_block and i not in f.fused]
+    red = [i for i in targets if i not in dgraph.row_block and i not in f.fused]
+    lf.peer_red = f.peer_reduce and bool(red) and bool(split_t)
+    if lf.peer_red and not f.peer_fit:
+        # (not an assert: under python -O the relation-sharded sums would silently go unreduced)
+        raise RuntimeError(f"layer {layer}: the peer all-reduce is on but its targets do not fit one epilogue launch")
+    return lf
+
+
+def decide_forms(dgraph: DeviceGraph, h1: int, h2: int, allreduce=None, keep_sums: bool = False,
+                 dropout=None, shard=None) -> PlanForms:
+    """The launch forms of ForwardPlan(dgraph, ..., h1, h2, allreduce, keep_sums, dropout, shard),
+    decided once and before any buffer is allocated, from host metadata alone: the device
+    graph's group records, the shard, the widths and this module's policy.  No device tensor's
+    data is read."""
+    if shard is not None:
+        allreduce = shard.allreduce
+    groups, row_block, edge_types = dgraph.groups, dgraph.row_block, list(dgraph.edge_types)
+    targets = _targets(dgraph)
+    rels = {et: groups[et].n_rels for et in edge_types}
+    dropping = dropout is not None and float(dropout[0]) < 1.0
+    plain = not keep_sums and not dropping  # forward only, no dropout
+    wide = h1 == 64 and h2 == 32            # the shape of the seg kernels' reassociated layer 2
+    # flat mode: every group's pre-normalisation sum S_ij lands in one flat buffer per
+    # layer (all-reduced when sharded; kept for the backward when training), and one fused
+    # launch over dense-rows groups (DG_GROUP_DENSE_ROWS) finishes every node type from it
+    f = PlanForms(flat_mode=allreduce is not None or keep_sums)
+    f.fused = _fused_targets(dgraph, targets, allreduce is not None, keep_sums, getattr(shard, "fused_rows", False))
+    if keep_sums and allreduce is None:
+        # one GPU, training: when no node type would take the fused path anyway (config P),
+        # keep the partial-mode layers and let their one epilogue launch also write every
+        # group's pre-normalisation sum S_ij — no flat reduces, no finishing launch
+        f.sums_mode = not f.fused
+        f.flat_mode, f.fused = bool(f.fused), []
+    # config S's weak scaling (RelationShard.weak_sets form "seg"): every node type row-split,
+    # its groups in dg_spmm_seg_f32 (one wave per (row, relation), one chunk per relation
+    # set) + the epilogue, and layer 2 reassociated, Σ_k (Â_k·H1_j)·W2_k — no projection
+    # GEMM over every relation on every rank (forward only: the backward keeps the sums)
+    f.seg_mode = (shard is not None and getattr(shard, "seg_rows", False) and plain and wide
+                  and all(et[0] in row_block for et in edge_types)
+                  and all(g.seg is not None or not g.n_rels for g in groups.values()))
+    # (otherwise such a shard runs the same chunks in dg_spmm_groups_f32 + the epilogue,
+    # with the projection GEMM)
+    # the peer all-reduce (config P's drug rows, peer mode "fused"): the relation-sharded
+    # groups' pre-normalisation sums of layer L live in `world` slots of the region, slot r
+    # written by rank r's epilogue launch into every rank's copy; the finishing launch adds
+    # the slots in rank order (dense-rows groups with n_chunks = world) — no RCCL all-reduce
+    pc = getattr(shard, "peer", None)
+    if (pc is not None and pc.mode == "fused" and f.flat_mode and plain and not f.seg_mode and not f.fused
+            and any(i in row_block for i in targets)):
+        f.peer_fit = _peer_reduce_fits(dgraph, targets)
+        f.peer_reduce = f.peer_fit
+    # staged groups make their slabs H1_j·W2_k in the layer-2 kernel itself
+    # (dg_spmm_staged_proj_f32): no P buffer, no GEMM for them (64-wide H1, no dropout)
+    f.staged_proj = {et for et in edge_types
+                     if groups[et].staged and rels[et] and h1 == 64 and not dropping and STAGED_PROJ}
+    # one GPU (config S): every node type finished by dg_gcn_fused_seg_f32 — one workgroup
+    # per row, one wave per relation — with layer 2 reassociated (no projection in layer 1,
+    # no GEMM), when every group is one chunk of <= 16 relations per row in total
+    f.fused_seg = (FUSED_SEG and not f.flat_mode and not row_block and not dropping and wide
+                   and all(g.seg is not None and g.n_chunks == 1 and g.chunk == g.n_rels >= 1
+                           and not g.staged for g in groups.values())
+                   and all(sum(rels[et] for et in ets) <= 16 for ets in targets.values()))
+    if f.fused_seg:
+        f.fused = list(targets)
+    # ... or, L2_PREPROJECT, layer 2's operands made by layer 1's launch (plan.proj), layer 2 a
+    # plain gather-sum over them: a one-GPU forward-only plan in the wave-table fused form
+    if f.fused_seg and WAVE_TABLE and plain and shard is None:
+        # TAB_WEIGHTED: where a weighted workgroup also has the wave slots for a row's jobs.  (Read
+        # by layer 1 with L2_PREPROJECT = 0 too: the plan's A/B fallback keeps layer 1's table, a
+        # row's waves and so H1's bits, and differs in layer 2 alone.)
+        fits, f.tab_weighted = _preproject_fit(targets, rels, h1)
+        if fits and L2_PREPROJECT:
+            f.preproj = set(edge_types)
+    if wide and (f.seg_mode or f.fused_seg):
+        f.seg_proj = {et for et in edge_types if rels[et] and et not in f.preproj}
+    # sharded forward plans: every other non-staged group's layer 2 reassociated as well, over
+    # the rank's own rows / relations (config P: PPI in its one-chunk layout, (0,1), (1,0)),
+    # so no rank runs a projection GEMM over all of H1 (REASSOC_ROWS)
+    if REASSOC_ROWS and shard is not None and plain and wide:
+        f.seg_proj |= {et for et in edge_types if rels[et] and not groups[et].staged
+                       and (groups[et].seg is not None or groups[et].seg2 is not None)}
+    # layer-1 rows finished by a fused launch (the SpMM one, or — sharded — the one that
+    # finishes the all-reduced sums) project themselves onto the layer-2 relations
+    rels_from: Dict[int, int] = {}
+    for et in edge_types:
+        rels_from[et[1]] = rels_from.get(et[1], 0) + rels[et]
+    finished = (set(targets) - set(row_block)) if f.flat_mode else set(f.fused)
+    f.proj_fused = [et for et in edge_types
+                    if rels[et] and et[1] in finished and et not in f.staged_proj | f.seg_proj | f.preproj
+                    and rels_from[et[1]] <= ForwardPlan.FUSED_PROJ_MAX_RELS and not dropping]
+    if len(f.proj_fused) > DG_MAX_GROUPS:
+        f.proj_fused = []
+    f.layers = {layer: _layer_forms(f, dgraph, layer, h1, h2) for layer in (1, 2)}
+    return f
+
+
+@dataclass
+class _L2Tab:
+    """Layer 2's 32 -> 32 wave-table launch as built (attach_decoder_rows rebuilds it with the
+    decoder's row operands)."""
+
+    targets: list
+    nodes: List[int]  # the targets' node types
+    plain: "kernels.PreparedFusedTab"  # the launch without a decoder: its widths, balance, weighted
+
+
 class ForwardPlan:
     """All buffers and prepared launches of one two-layer forward on one device."""
 
@@ -551,21 +773,7 @@ class ForwardPlan:
                  dropout: Optional[Tuple[float, torch.Tensor]] = None, shard=None):
         self.g = dgraph
         self.h1, self.h2 = h1, h2
-        # multi-GPU (sharding.RelationShard): the collectives joining the ranks' shares —
-        # all-reduce of the relation-sharded node types' sums, all-gather of the row-split
-        # node types' finished row blocks
-        self.shard = shard
-        if shard is not None:
-            allreduce = shard.allreduce
-        self.allreduce = allreduce
-        self.row_block = dict(dgraph.row_block)
-        self.world = shard.world_size if shard is not None else 1
-        self.allgather = shard.allgather if shard is not None else None
-        if self.row_block and (shard is None or shard.row_block != self.row_block
-                               or (self.allgather is None and getattr(shard, "peer", None) is None)):
-            raise ValueError("a row-split device graph needs its RelationShard (with an all-gather or a peer exchange)")
-        if shard is not None and allreduce is None:
-            raise ValueError("a RelationShard needs its all-reduce")
+        self._check_shard(shard, allreduce)
         # dropout (training): (keep probability, device state {seed, step}); every forward
         # draws new masks (the step advances first), the backward reuses them
         # (sharded: a relation's masks are keyed by its GLOBAL id, so every rank — and one GPU —
@@ -573,49 +781,58 @@ class ForwardPlan:
         self.keep, self.drop_state = 1.0, None
         if dropout is not None and float(dropout[0]) < 1.0:
             self.keep, self.drop_state = float(dropout[0]), dropout[1]
-        # flat mode: every group's pre-normalisation sum S_ij lands in one flat buffer per
-        # layer (all-reduced when sharded; kept for the backward when training), and one fused
-        # launch over dense-rows groups (DG_GROUP_DENSE_ROWS) finishes every node type from it
-        self.flat_mode = allreduce is not None or keep_sums
         self.keep_sums = keep_sums
-        self.sums_mode = False  # set below: partial mode whose epilogue also writes each S_ij
         self.launch_groups: Dict[int, List[EdgeType]] = {}  # id(SpMM launch) -> its groups
         self.runs = 0     # run() calls so far (decoder_rows_valid)
         self._dec = None  # the attached decoder's row operands (attach_decoder_rows)
         self._dec_retired: list = []
-        dev = dgraph.device
-        f32 = dict(device=dev, dtype=torch.float32)
+        self._l2_tab: Optional[_L2Tab] = None
+        self._f32 = dict(device=dgraph.device, dtype=torch.float32)
         self.edge_types = list(dgraph.edge_types)
-        self.targets: Dict[int, List[EdgeType]] = {}
-        for et in self.edge_types:
-            self.targets.setdefault(et[0], []).append(et)
-        if any(len(v) > DG_MAX_GROUPS for v in self.targets.values()):
-            raise ValueError(f"more than {DG_MAX_GROUPS} edge types into one node type")
-        if keep_sums and allreduce is None:
-            # one GPU, training: when no node type would take the fused path anyway (config P),
-            # keep the partial-mode layers and let their one epilogue launch also write every
-            # group's pre-normalisation sum S_ij — no flat reduces, no finishing launch
-            self.flat_mode = False
-            if not self._fused_targets():
-                self.sums_mode = True
-            else:
-                self.flat_mode = True
-        n = dgraph.n_nodes
-        # config S's weak scaling (RelationShard.weak_sets form "seg"): every node type row-split,
-        # its groups in dg_spmm_seg_f32 (one wave per (row, relation), one chunk per relation
-        # set) + the epilogue, and layer 2 reassociated, Σ_k (Â_k·H1_j)·W2_k — no projection
-        # GEMM over every relation on every rank (forward only: the backward keeps the sums)
-        self.seg_mode = (shard is not None and getattr(shard, "seg_rows", False) and not keep_sums
-                         and self.drop_state is None and h1 == 64 and h2 == 32
-                         and all(et[0] in self.row_block for et in self.edge_types)
-                         and all(g.seg is not None or not g.n_rels for g in dgraph.groups.values()))
-        # (otherwise such a shard runs the same chunks in dg_spmm_groups_f32 + the epilogue,
-        # with the projection GEMM)
+        self.targets = _targets(dgraph)
+        self.et_index = {et: n for n, et in enumerate(self.edge_types)}
+        # every form decision, before the first buffer
+        self.forms = decide_forms(dgraph, h1, h2, self.allreduce, keep_sums, dropout, shard)
+        for name in FORM_ATTRS:  # (readable on the plan as before the decision was split out)
+            setattr(self, name, getattr(self.forms, name))
+        x1 = self._layer1_operands(features, w1)
+        self._exchange_region()
+        self._outputs()
+        self._projection_buffers(w2)
+        # ---- layer 1 (+ the layer-2 projections of rows it finishes) ----
+        self._layer1 = self._build_layer(1, x1, self._fused_projections(w2),
+                                         post={et: w2.stacks[et] for et in self.edge_types if et in self.preproj})
+        # ---- layer 2: remaining projections in one batched MFMA GEMM launch, then SpMM ----
+        self._layer2_operands(w2)
+        self._layer2 = self._build_layer(2, self.proj,
+                                         staged_proj={et: (self.hidden1[et[1]], w2.stacks[et])
+                                                      for et in self.staged_proj},
+                                         seg_w={et: (self.hidden1[et[1]], w2.stacks[et]) for et in self.seg_proj})
 
-        # ---- layer-1 dense operand: W1 (identity features) or X_j·W1_k (sparse features) ----
+    # ------------------------------------------------------------------ buffers and operands
+    def _check_shard(self, shard, allreduce) -> None:
+        """multi-GPU (sharding.RelationShard): the collectives joining the ranks' shares —
+        all-reduce of the relation-sharded node types' sums, all-gather of the row-split
+        node types' finished row blocks"""
+        self.shard = shard
+        if shard is not None:
+            allreduce = shard.allreduce
+        self.allreduce = allreduce
+        self.row_block = dict(self.g.row_block)
+        self.world = shard.world_size if shard is not None else 1
+        self.allgather = shard.allgather if shard is not None else None
+        if self.row_block and (shard is None or shard.row_block != self.row_block
+                               or (self.allgather is None and getattr(shard, "peer", None) is None)):
+            raise ValueError("a row-split device graph needs its RelationShard (with an all-gather or a peer exchange)")
+        if shard is not None and allreduce is None:
+            raise ValueError("a RelationShard needs its all-reduce")
+
+    def _layer1_operands(self, features, w1: LayerWeights) -> Dict[EdgeType, torch.Tensor]:
+        """Layer 1's dense operand per group: W1 (identity features) or X_j·W1_k (sparse
+        features), and the launches that make them each forward (self._pre)."""
+        dgraph, n, dev, h1 = self.g, self.g.n_nodes, self.g.device, self.h1
         self._pre: List[Callable[[], None]] = []
         x1: Dict[EdgeType, torch.Tensor] = {}
-        self.et_index = {et: n for n, et in enumerate(self.edge_types)}
         if self.drop_state is not None:
             self._pre.append(lambda st=self.drop_state: kernels.dropout_advance(st))
         for et in self.edge_types:
@@ -651,7 +868,7 @@ class ForwardPlan:
             # all of them — sparse features are small next to the adjacency): one copy of X_j's
             # pattern shared by the K chunks, chunk k reading W1_k; with dropout, chunk k masks
             # X_j's values with its own draw (dropout_sparse per relation, layers.py:23-31, :88)
-            xw = torch.empty((K, n[j], h1), **f32)
+            xw = torch.empty((K, n[j], h1), **self._f32)
             drop = (None if self.drop_state is None
                     else (self.drop_state, drop_tag(1, self.et_index[et]), self.keep))
             spec = kernels.RelGroupSpec(torch.from_numpy(fj.rowptr).to(dev), torch.from_numpy(fj.col).to(dev),
@@ -659,158 +876,115 @@ class ForwardPlan:
                                         vcol_max=int(fj.col.max()) if fj.nnz else -1, shared=True, drop=drop)
             self._pre.append(kernels.PreparedSpmm([spec], h1))
             x1[et] = xw
+        return x1
 
-        # row-split node types: the full output rows live in a buffer padded to world × block
-        # rows (this rank finishes its block in place, the all-gather fills the rest)
-        # (keyed by node type and layer: h1 == h2 must not share a buffer).  Every such buffer
-        # is carved from ONE exchange region with the same layout on every rank, which a peer
-        # exchange (peer.py) maps into every peer
+    def _exchange_region(self) -> None:
+        """Row-split node types: the full output rows live in a buffer padded to world × block
+        rows (this rank finishes its block in place, the all-gather fills the rest), keyed by
+        node type and layer: h1 == h2 must not share a buffer.  Every such buffer is carved from
+        ONE exchange region with the same layout on every rank, which a peer exchange (peer.py)
+        maps into every peer — with, for the peer all-reduce, the world slots of each layer's
+        relation-sharded sums behind them."""
+        n = self.g.n_nodes
         self._pad: Dict[Tuple[int, int], torch.Tensor] = {}
         self.xregion: Optional[torch.Tensor] = None
         self.peer = None
-        split_nodes = [i for i in self.targets if i in self.row_block]
-        # the peer all-reduce (config P's drug rows, peer mode "fused"): the relation-sharded
-        # groups' pre-normalisation sums of layer L live in `world` slots of the region, slot r
-        # written by rank r's epilogue launch into every rank's copy; the finishing launch adds
-        # the slots in rank order (dense-rows groups with n_chunks = world) — no RCCL all-reduce
-        pc = getattr(shard, "peer", None)
-        self.peer_reduce = (pc is not None and pc.mode == "fused" and self.flat_mode and not keep_sums
-                            and self.drop_state is None and bool(split_nodes) and not self.seg_mode
-                            and not self._fused_targets() and self._peer_reduce_fits(dgraph, split_nodes))
         self._red_slots: Dict[Tuple[int, EdgeType], torch.Tensor] = {}  # (layer, et) -> [world, n_i, d] view
-        if split_nodes:
-            layout, off = {}, 0
-            for layer, d in ((1, h1), (2, h2)):
-                for i in split_nodes:
-                    nb = self.world * self.row_block[i][2] * d
-                    layout[i, layer] = (off, nb, d)
-                    off += -(-nb // 64) * 64  # 256-byte aligned
-            red_layout = {}
-            if self.peer_reduce:
-                for layer, d in ((1, h1), (2, h2)):
-                    red = [et for et in self.edge_types if et[0] not in self.row_block]
-                    per = sum(n[et[0]] * d for et in red)  # one slot: every group's rows, in order
-                    per = -(-per // 64) * 64
-                    o2 = 0
-                    for et in red:
-                        red_layout[layer, et] = (off, o2, per, n[et[0]], d)
-                        o2 += n[et[0]] * d
-                    off += self.world * per
-            # zeros: a slot no rank ever pushes (a group without relations on that rank) reads as
-            # zeros forever
-            if pc is not None and pc.region_kind:  # (uncached by default: peer.PeerConfig)
-                from .peer import device_tensor
+        split_nodes = [i for i in self.targets if i in self.row_block]
+        if not split_nodes:
+            return
+        pc = getattr(self.shard, "peer", None)
+        layout, off = {}, 0
+        for layer, d in ((1, self.h1), (2, self.h2)):
+            for i in split_nodes:
+                nb = self.world * self.row_block[i][2] * d
+                layout[i, layer] = (off, nb, d)
+                off += -(-nb // 64) * 64  # 256-byte aligned
+        red_layout = {}
+        if self.peer_reduce:
+            for layer, d in ((1, self.h1), (2, self.h2)):
+                red = [et for et in self.edge_types if et[0] not in self.row_block]
+                per = sum(n[et[0]] * d for et in red)  # one slot: every group's rows, in order
+                per = -(-per // 64) * 64
+                o2 = 0
+                for et in red:
+                    red_layout[layer, et] = (off, o2, per, n[et[0]], d)
+                    o2 += n[et[0]] * d
+                off += self.world * per
+        # zeros: a slot no rank ever pushes (a group without relations on that rank) reads as
+        # zeros forever
+        if pc is not None and pc.region_kind:  # (uncached by default: peer.PeerConfig)
+            self.xregion = device_tensor(max(off, 64), pc.region_kind, self.g.device)
+        else:
+            self.xregion = torch.zeros(max(off, 64), **self._f32)
+        for (i, layer), (o, nb, d) in layout.items():
+            self._pad[i, layer] = self.xregion[o:o + nb].view(-1, d)
+        for key, (base, o2, per, rows, d) in red_layout.items():
+            self._red_slots[key] = torch.as_strided(self.xregion, (self.world, rows, d), (per, d, 1), base + o2)
+        if pc is not None:
+            self.peer = PeerExchange(self.xregion, self.shard.rank, self.world, pc)
 
-                self.xregion = device_tensor(max(off, 64), pc.region_kind, dev)
-            else:
-                self.xregion = torch.zeros(max(off, 64), **f32)
-            for (i, layer), (o, nb, d) in layout.items():
-                self._pad[i, layer] = self.xregion[o:o + nb].view(-1, d)
-            for key, (base, o2, per, rows, d) in red_layout.items():
-                self._red_slots[key] = torch.as_strided(self.xregion, (self.world, rows, d), (per, d, 1),
-                                                        base + o2)
-            if pc is not None:
-                from .peer import PeerExchange
-
-                self.peer = PeerExchange(self.xregion, shard.rank, self.world, pc)
+    def _outputs(self) -> None:
+        n = self.g.n_nodes
 
         def out_buf(i, d, layer):
             if i not in self.row_block:
-                return torch.empty((n[i], d), **f32)
+                return torch.empty((n[i], d), **self._f32)
             return self._pad[i, layer][:n[i]]
 
-        self.hidden1 = {i: out_buf(i, h1, 1) for i in self.targets}
-        self.embeddings = {i: out_buf(i, h2, 2) for i in self.targets}
+        self.hidden1 = {i: out_buf(i, self.h1, 1) for i in self.targets}
+        self.embeddings = {i: out_buf(i, self.h2, 2) for i in self.targets}
+        self._outs = {1: self.hidden1, 2: self.embeddings}  # by layer
         for i, e in self.embeddings.items():  # (a decoder built on one finds this plan from the tensor)
             kernels.register_row_producer(e, self, i)
 
-        # ---- layer-2 projection buffers P_k = H1_j·W2_k (global slabs) ----
-        # staged groups make their slabs H1_j·W2_k in the layer-2 kernel itself
-        # (dg_spmm_staged_proj_f32): no P buffer, no GEMM for them (64-wide H1, no dropout)
-        self.staged_proj = {et for et in self.edge_types
-                            if dgraph.groups[et].staged and dgraph.groups[et].n_rels and h1 == 64
-                            and self.drop_state is None and STAGED_PROJ}
-        # one GPU (config S): every node type finished by dg_gcn_fused_seg_f32 — one workgroup
-        # per row, one wave per relation — with layer 2 reassociated (no projection in layer 1,
-        # no GEMM), when every group is one chunk of <= 16 relations per row in total
-        self.fused_seg = (FUSED_SEG and not self.flat_mode and not self.row_block and self.drop_state is None
-                          and h1 == 64 and h2 == 32
-                          and all(g.seg is not None and g.n_chunks == 1 and g.chunk == g.n_rels >= 1
-                                  and not g.staged for g in dgraph.groups.values())
-                          and all(sum(dgraph.groups[et].n_rels for et in ets) <= 16
-                                  for ets in self.targets.values()))
-        # ... or, L2_PREPROJECT, layer 2's operands made by layer 1's launch (self.proj), layer 2 a
-        # plain gather-sum over them
-        self.preproj = set(self.edge_types) if self._preproject_fits(keep_sums) else set()
-        self.seg_proj = {et for et in self.edge_types
-                         if (self.seg_mode or self.fused_seg) and dgraph.groups[et].n_rels and h1 == 64 and h2 == 32
-                         and et not in self.preproj}
-        # sharded forward plans: every other non-staged group's layer 2 reassociated as well, over
-        # the rank's own rows / relations (config P: PPI in its one-chunk layout, (0,1), (1,0)),
-        # so no rank runs a projection GEMM over all of H1 (REASSOC_ROWS)
-        self.seg_proj |= {et for et in self.edge_types
-                          if REASSOC_ROWS and shard is not None and not keep_sums and self.drop_state is None
-                          and h1 == 64 and h2 == 32 and dgraph.groups[et].n_rels and not dgraph.groups[et].staged
-                          and (dgraph.groups[et].seg is not None or dgraph.groups[et].seg2 is not None)}
-        self.seg_l1 = {et for et in self.edge_types
-                       if SEG_ROWS_L1 and shard is not None and not self.seg_mode and not keep_sums
-                       and self.drop_state is None and h1 in (32, 64) and et[0] in self.row_block
-                       and dgraph.groups[et].n_rels and not dgraph.groups[et].staged
-                       and dgraph.groups[et].seg is not None}
+    def _projection_buffers(self, w2: LayerWeights) -> None:
+        """Layer 2's operands P_k = H1_j·W2_k (global slabs) of the groups that are neither
+        staged-projected nor reassociated."""
+        h1, h2 = self.h1, self.h2
         self.proj: Dict[EdgeType, torch.Tensor] = {}
         for et in self.edge_types:
-            grp = dgraph.groups[et]
+            grp = self.g.groups[et]
             K, din, dout = w2.stacks[et].shape
             if din != h1 or dout != h2 or K != grp.K:
                 raise ValueError(f"layer-2 weights of {et} are {(K, din, dout)}, expected ({grp.K}, {h1}, {h2})")
             if et[1] not in self.hidden1:
                 raise ValueError(f"node type {et[1]} has no incoming edge type; layer 2 needs hidden1[{et[1]}]")
             if et not in self.staged_proj and et not in self.seg_proj:
-                self.proj[et] = torch.empty((K, n[et[1]], h2), **f32)
+                self.proj[et] = torch.empty((K, self.g.n_nodes[et[1]], h2), **self._f32)
 
-        # a second stream: a layer's gather-bound launch (dg_spmm_groups_f32) runs beside its
-        # LDS-bound staged launch (dg_spmm_staged_f32) — different units, no data dependence
-        self.side_stream = (torch.cuda.Stream(dev) if dev.type == "cuda" and CONCURRENT_LAUNCHES else None)
-
-        # ---- layer 1 (+ the layer-2 projections of rows it finishes) ----
-        self.fused = list(self.targets) if self.fused_seg else self._fused_targets()
-        rels_from: Dict[int, int] = {}
-        for et in self.edge_types:
-            rels_from[et[1]] = rels_from.get(et[1], 0) + dgraph.groups[et].n_rels
-        # layer-1 rows finished by a fused launch (the SpMM one, or — sharded — the one that
-        # finishes the all-reduced sums) project themselves onto the layer-2 relations
-        finished = (set(self.targets) - set(self.row_block)) if self.flat_mode else set(self.fused)
-        proj_fused = [et for et in self.edge_types
-                      if dgraph.groups[et].n_rels and et[1] in finished and et not in self.staged_proj
-                      and et not in self.seg_proj and et not in self.preproj
-                      and rels_from[et[1]] <= self.FUSED_PROJ_MAX_RELS and self.drop_state is None]
-        if len(proj_fused) > DG_MAX_GROUPS:
-            proj_fused = []
+    def _fused_projections(self, w2: LayerWeights):
+        """(source node type, ProjSpec) of forms.proj_fused: the launch that finishes H1_j aims
+        each at its target (_retarget)."""
         projs = []
-        for et in proj_fused:
-            grp = dgraph.groups[et]
+        for et in self.forms.proj_fused:
+            grp = self.g.groups[et]
             projs.append((et[1], kernels.ProjSpec(
                 w2.stacks[et], self.proj[et], grp.n_rels, -1, rel_map=grp.rel_map,
                 rel_map_max=int(grp.rel_ids.max()) if grp.rel_map is not None else None)))
-        self._layer1 = self._build_layer(x1, h1, True, f32, projs,
-                                         post={et: w2.stacks[et] for et in self.edge_types if et in self.preproj})
+        return projs
 
-        # ---- layer 2: remaining projections in one batched MFMA GEMM launch, then SpMM ----
+    def _layer2_operands(self, w2: LayerWeights) -> None:
+        """self._gemm2: the remaining projections in batched MFMA GEMM launches, after (training)
+        the dropout of their operands."""
+        n, dev, h1, h2 = self.g.n_nodes, self.g.device, self.h1, self.h2
+        made = set(self.forms.proj_fused) | self.staged_proj | self.seg_proj | self.preproj
         gemms, drops = [], []
         self.hdrop: Dict[EdgeType, torch.Tensor] = {}
         for et in self.edge_types:
-            grp = dgraph.groups[et]
-            if not grp.n_rels or et in proj_fused or et in self.staged_proj or et in self.seg_proj \
-                    or et in self.preproj:
+            grp = self.g.groups[et]
+            if not grp.n_rels or et in made:
                 continue
             j = et[1]
             W = w2.stacks[et]
+            a, sa, b_map = self.hidden1[j], (0, h1, 1), grp.rel_map
+            b_max = int(grp.rel_ids.max()) if b_map is not None else None
             if self.drop_state is not None:
                 # tf.nn.dropout(H1_j) drawn per relation (layers.py:111-113): H_k = M_k∘H1_j/keep,
                 # one slab per LOCAL relation in ascending relation id (the backward's dP order;
                 # sharded: slab b is relation sorted_ids[b], its mask drawn under that global id),
                 # projected into P's global slabs
-                hd = torch.empty((grp.n_rels, n[j], h1), **f32)
+                hd = torch.empty((grp.n_rels, n[j], h1), **self._f32)
                 self.hdrop[et] = hd
                 t = drop_tag(2, self.et_index[et])
                 sids = np.sort(grp.rel_ids).astype(np.int32)
@@ -821,398 +995,339 @@ class ForwardPlan:
                 else:
                     drops.append(lambda j=j, hd=hd, t=t, m=smap, mx=int(sids.max()): kernels.dropout_elems_map(
                         self.hidden1[j], hd, m, self.drop_state, t, self.keep, rel_map_max=mx))
-                gemms.append(kernels.PreparedGemm(
-                    hd, (n[j] * h1, h1, 1), W, (h1 * h2, h2, 1), self.proj[et], (n[j] * h2, h2, 1),
-                    n[j], h2, h1, grp.n_rels, b_map=smap, b_batches=W.shape[0],
-                    b_map_max=int(sids.max()) if smap is not None else None))
-                continue
-            gemms.append(kernels.PreparedGemm(
-                self.hidden1[j], (0, h1, 1), W, (h1 * h2, h2, 1), self.proj[et], (n[j] * h2, h2, 1),
-                n[j], h2, h1, grp.n_rels, b_map=grp.rel_map, b_batches=W.shape[0],
-                b_map_max=int(grp.rel_ids.max()) if grp.rel_map is not None else None))
+                a, sa, b_map, b_max = hd, (n[j] * h1, h1, 1), smap, (int(sids.max()) if smap is not None else None)
+            gemms.append(kernels.PreparedGemm(a, sa, W, (h1 * h2, h2, 1), self.proj[et], (n[j] * h2, h2, 1), n[j], h2, h1,
+                                              grp.n_rels, b_map=b_map, b_batches=W.shape[0], b_map_max=b_max))
         self._gemm2 = drops + [kernels.PreparedGemmMulti(gemms[s:s + DG_MAX_GROUPS])
                                for s in range(0, len(gemms), DG_MAX_GROUPS)]
-        self._layer2 = self._build_layer(self.proj, h2, False, f32,
-                                         staged_proj={et: (self.hidden1[et[1]], w2.stacks[et])
-                                                      for et in self.staged_proj},
-                                         seg_w={et: (self.hidden1[et[1]], w2.stacks[et]) for et in self.seg_proj})
 
-    # ------------------------------------------------------------------ layer builder
-    def _fused_targets(self) -> List[int]:
-        """Node types one dg_gcn_fused_f32 launch finishes: at most FUSED_MAX_ROWS (local) rows,
-        every group one chunk (and not staged).  Sharded plans finish only row-split node types
-        this way, when the shard asks for it (`fused_rows`: their rows are complete on this
-        rank; relation-sharded ones need the all-reduce first), and the sharded backward takes
-        none."""
-        if self.flat_mode and (self.keep_sums or not self.row_block
-                               or not getattr(self.shard, "fused_rows", False)):
-            return []
-
-        def rows(i):
-            if i in self.row_block:
-                return self.row_block[i][1] - self.row_block[i][0]
-            return self.g.n_nodes[i]
-
-        return [i for i, ets in self.targets.items()
-                if (not self.flat_mode or i in self.row_block)
-                and 0 < rows(i) <= FUSED_MAX_ROWS
-                and all(self.g.groups[et].n_chunks == 1 and self.g.groups[et].n_rels > 0
-                        and not self.g.groups[et].staged for et in ets)]
-
-    def _preproject_fits(self, keep_sums: bool) -> bool:
-        """L2_PREPROJECT's conditions: a one-GPU forward-only plan whose layers run the wave-table
-        fused form, with a wave slot in layer 1's workgroups for every (row, sourced relation)."""
-        self.tab_weighted = False
-        if not (self.fused_seg and WAVE_TABLE and not keep_sums and self.drop_state is None and self.shard is None):
-            return False
-        order = list(self.targets)
-        if any(et[1] not in self.targets for et in self.edge_types):
-            return False
-        if any(len(self.targets[i]) > 64 // (self.h1 // 4) for i in order):  # (_tab_groups_fit, both layers)
-            return False
-        rels = {et: self.g.groups[et].n_rels for et in self.edge_types}
-        waves_t = [sum(rels[et] for et in self.targets[i]) for i in order]
-        sourced_t = [sum(k for et, k in rels.items() if et[1] == i) for i in order]
-        if not wavetable.tab_proj_fit(waves_t, sourced_t, _tab_balance(self.h1, self.h1), L2_PREPROJECT_SHARE):
-            return False
-        # TAB_WEIGHTED: where a weighted workgroup also has the wave slots for a row's jobs.  (Read
-        # by layer 1 with L2_PREPROJECT = 0 too: the plan's A/B fallback keeps layer 1's table, a
-        # row's waves and so H1's bits, and differs in layer 2 alone.)
-        self.tab_weighted = wavetable.weighted_proj_fit(sourced_t, L2_PREPROJECT_SHARE)
-        return bool(L2_PREPROJECT)
-
+    # ------------------------------------------------------------------ layer builders
     def _spec(self, et, x: torch.Tensor, out, d) -> kernels.RelGroupSpec:
         grp = self.g.groups[et]
         return kernels.RelGroupSpec(grp.rowptr, grp.vcol, grp.val, x, out, grp.n_rows, grp.n_chunks, d,
                                     grp.K * grp.n_cols, vcol_max=grp.vcol_max)
 
-    def _seg_spec(self, et, x: torch.Tensor, out=None, w=None) -> kernels.SegSpec:
+    def _seg_spec(self, et, xs, seg_w, out=None) -> kernels.SegSpec:
+        """A group's seg spec over its layer's operand: layer 2 reassociated (seg_w) reads H1_j
+        and W2's stack, otherwise xs[et]."""
         grp = self.g.groups[et]
-        if grp.seg is None and grp.seg2 is not None:  # a windowed group's one-chunk layout
-            rp, vc, vv, sg, ch, nc, vmax = grp.seg2
-        else:
-            rp, vc, vv, sg, ch, nc, vmax = grp.rowptr, grp.vcol, grp.val, grp.seg, grp.chunk, grp.n_chunks, grp.vcol_max
+        x, w = seg_w[et] if et in seg_w else (xs[et], None)
+        rp, vc, vv, sg, ch, nc, vmax = self._seg_layout(grp)
         return kernels.SegSpec(rp, sg, vc, vv, x, out, grp.n_rows, grp.n_cols, nc, ch, grp.n_rels, x.stride(-2),
                                grp.K * grp.n_cols, vcol_max=vmax, w=w, slab=grp.rel_map,
                                slab_max=int(grp.rel_ids.max()) if grp.n_rels else -1)
 
-    def _seg_chunks(self, et) -> int:
-        grp = self.g.groups[et]
-        return grp.seg2[5] if (grp.seg is None and grp.seg2 is not None) else grp.n_chunks
+    @staticmethod
+    def _seg_layout(grp: DeviceGroup) -> tuple:
+        """(rowptr, vcol, val, seg, chunk, n_chunks, vcol_max) of a group's seg launches."""
+        if grp.seg is None and grp.seg2 is not None:  # a windowed group's one-chunk layout
+            return grp.seg2
+        return grp.rowptr, grp.vcol, grp.val, grp.seg, grp.chunk, grp.n_chunks, grp.vcol_max
 
-    def _build_layer(self, xs: Dict[EdgeType, torch.Tensor], d, relu, f32, projs=(), staged_proj=None, seg_w=None,
-                     post=None):
-        """Prepared launches of one layer: fused targets in one dg_gcn_fused_f32 launch; the
-        other targets' groups in partial mode + epilogue — with, when sharded, the chunk
-        reduce into the all-reduce buffer and the all-reduce before the epilogue."""
-        g = self.g
-        n = g.n_nodes
-        outs = self.hidden1 if relu else self.embeddings
-        launches: List[Callable[[], None]] = []
-        fused_t = self.fused
-        gathers = []
-        if self.seg_mode and SEG_FUSED and all(sum(g.groups[et].n_rels for et in ets) <= SEG_FUSED_MAX_ITEMS
-                                               for ets in self.targets.values()):
-            # every node type row-split: one launch finishes this rank's row block of each
-            # (its workgroups' waves loop over the N relation sets), then the all-gathers
-            seg_w = seg_w or {}
-            tgts = []
-            for i in self.targets:
-                a, b, blk = self.row_block[i]
-                pad = self._pad[i, 1 if relu else 2]
-                r0 = self.shard.rank * blk
-                gathers.append((pad, pad[r0:r0 + blk]))
-                tgts.append((pad[r0:r0 + (b - a)], b - a,
-                             [self._seg_spec(et, seg_w[et][0], None, seg_w[et][1]) if et in seg_w
-                              else self._seg_spec(et, xs[et]) for et in self.targets[i]], relu))
-            fused_peer = self._peer_fused(relu)
-            d_in = self.h1 if seg_w else d
-            if WAVE_TABLE and d_in == 64 and (d == 64 or seg_w) and _tab_groups_fit(tgts, d):
-                # (one wave per relation here: dealing the pairs of N = 2's 14-relation rows over
-                # 16 wave slots measured 16.45 / 23.04 µs a rank against 16.39 / 22.65, RCCL no-op /
-                # peer loopback, round 6)
-                launches.append(kernels.PreparedFusedTab(tgts, d_in, d, peer=fused_peer, balance=False))  # (the wave-table form)
-            else:
-                launches.append(kernels.PreparedFusedSeg(tgts, d_in, d, peer=fused_peer))
-            self.launch_groups[id(launches[-1])] = [et for i in self.targets for et in self.targets[i]]
-            if fused_peer is not None:
-                gathers = []  # the launch itself ends with the exchange
-            return _Layer(launches, None, False, self.allreduce, [], [], {}, self.side_stream, None, (), gathers,
-                          self.allgather, self._peer_gather_all(gathers, relu))
-        if self.fused_seg:
-            seg_w = seg_w or {}
-            tgts = [(outs[i], n[i], [self._seg_spec(et, seg_w[et][0], None, seg_w[et][1]) if et in seg_w
-                                     else self._seg_spec(et, xs[et]) for et in self.targets[i]], relu)
-                    for i in fused_t]
-            d_in = self.h1 if seg_w else d
-            if WAVE_TABLE and d_in == 64 and (d == 64 or seg_w) and _tab_groups_fit(tgts, d):
-                # the wave-table form: the same rows bitwise, fewer dependent loads a wave
-                # (post: layer 1 also projecting its rows onto layer 2's relations, L2_PREPROJECT)
-                pj = []
-                for et, W2 in (post or {}).items():
-                    grp = g.groups[et]
-                    pj.append(kernels.TabProjSpec(fused_t.index(et[1]), W2, self.proj[et], grp.n_rels,
-                                                  None if grp.rel_map is None else grp.rel_map.cpu().numpy()))
-                launches.append(kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d), projs=pj,
-                                                         share_proj=L2_PREPROJECT_SHARE,
-                                                         weighted=_tab_weighted(d_in, d) if self.tab_weighted else 0))
-            elif WAVE_TABLE and self.preproj and d_in == d == 32 and _tab_groups_fit(tgts, d):
-                # layer 2 over the P stacks layer 1 made: layer 1's shape at half the width
-                weighted = _tab_weighted(d_in, d) if self.tab_weighted else 0
-                launches.append(kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d),
-                                                         weighted=weighted))
-                # (attach_decoder_rows rebuilds this launch with the decoder's row operands)
-                self._l2_tab = (tgts, d_in, d, _tab_balance(d_in, d), list(fused_t), launches[-1], weighted)
-            else:
-                launches.append(kernels.PreparedFusedSeg(tgts, d_in, d))
-            self.launch_groups[id(launches[-1])] = [et for i in fused_t for et in self.targets[i]]
-        elif fused_t:
-            # waves per group: small launches (latency-bound) split the densest row group's
-            # batches of 64 over up to two waves; big launches have parallelism to spare
-            avg = max(g.groups[et].nnz / max(1, g.groups[et].n_rows) for i in fused_t for et in self.targets[i])
-            max_groups = max(len(self.targets[i]) for i in fused_t)
-            rows = sum(g.groups[self.targets[i][0]].n_rows for i in fused_t)
-            # (row blocks of N relation sets — config S's weak scaling — have N times longer
-            # rows over 1/N of the rows: up to 16 waves per row there; measured at N = 8, rank
-            # 0's layer 1: 27.0 µs at 2 waves per group)
-            cap = 16 // max_groups if self.row_block else 2
-            wpg = 1 if rows >= 4096 else int(max(1, min(cap, 16 // max_groups, math.ceil(avg / 64.0))))
-            if knob("DG_WPG", 0):  # tuning override
-                wpg = max(1, min(knob("DG_WPG", 0), 16 // max_groups))
-            pspecs = []
-            for tgt_node, pj in projs:
-                if tgt_node in fused_t:  # (sharded: the finishing launch projects the others)
-                    pj.target = fused_t.index(tgt_node)
-                    pspecs.append(pj)
-            tgts = []
-            for i in fused_t:
-                out, rows_i = outs[i], n[i]
-                if i in self.row_block:
-                    # a row-split node type (sharded): this rank's block, finished in place in the
-                    # padded output, then all-gathered
-                    a, b, blk = self.row_block[i]
-                    pad = self._pad[i, 1 if relu else 2]
-                    r0 = self.shard.rank * blk
-                    out, rows_i = pad[r0:r0 + (b - a)], b - a
-                    gathers.append((pad, pad[r0:r0 + blk]))
-                tgts.append((out, rows_i, [self._spec(et, xs[et], None, d) for et in self.targets[i]], relu))
-            launches.append(kernels.PreparedFused(tgts, d, pspecs, wpg))
-            self.launch_groups[id(launches[-1])] = [et for i in fused_t for et in self.targets[i]]
-        rest = [et for et in self.edge_types if et[0] not in fused_t]
-        flags = DG_EPI_L2NORM | (DG_EPI_RELU if relu else 0)
+    def _seg_targets(self, rows: Dict[int, torch.Tensor], xs, seg_w, relu: bool) -> list:
+        """The target list of a fused-seg / wave-table launch finishing rows[i] of node type i."""
+        return [(out, out.shape[0], [self._seg_spec(et, xs, seg_w) for et in self.targets[i]], relu)
+                for i, out in rows.items()]
+
+    def _row_block_of(self, i: int, layer: int):
+        """A row-split node type's (padded output, this rank's block of it — what the all-gather
+        sends — and the block's finished rows, in place in the padded output)."""
+        a, b, blk = self.row_block[i]
+        pad = self._pad[i, layer]
+        r0 = self.shard.rank * blk
+        return pad, pad[r0:r0 + blk], pad[r0:r0 + (b - a)]
+
+    @staticmethod
+    def _retarget(projs, nodes: List[int]) -> list:
+        """The projection specs whose source rows a launch over `nodes` finishes, aimed at their
+        target's position in it (sharded: the finishing launch projects the others)."""
+        out = []
+        for tgt_node, pj in projs:
+            if tgt_node in nodes:
+                pj.target = nodes.index(tgt_node)
+                out.append(pj)
+        return out
+
+    def _build_layer(self, layer: int, xs: Dict[EdgeType, torch.Tensor], projs=(), staged_proj=None, seg_w=None,
+                     post=None) -> "_Layer":
+        """Prepared launches of one layer, in the form decide_forms chose: fused targets in one
+        launch; the other targets' groups in partial mode, then the finishing step — with, when
+        sharded, the chunk reduce into the all-reduce buffer and the all-reduce before it."""
+        lf = self.forms.layers[layer]
+        seg_w = seg_w or {}
+        if lf.kind == "seg_rows":
+            return self._build_seg_rows(lf, xs, seg_w)
+        L = _Layer(allreduce=self.allreduce, allgather=self.allgather, fused_targets=self.fused)
+        if lf.kind == "fused_seg":
+            self._build_fused_seg(L, lf, xs, seg_w, post or {})
+        elif lf.kind == "fused":
+            self._build_fused(L, lf, xs, projs)
+        rest = [et for et in self.edge_types if et[0] not in self.fused]
+        sviews = self._sum_buffers(L, lf, [et for et in rest if et[0] not in self.row_block])
+        partials, reduces = self._build_partial(L, lf, rest, xs, staged_proj or {}, seg_w, sviews)
         # row-split node types (sharded) not finished by the fused launch: their groups run in
         # partial mode over this rank's row block and one epilogue finishes the block before
         # the exchange
-        split_t = [i for i in self.targets if i in self.row_block and i not in fused_t]
-        red = [et for et in rest if et[0] not in self.row_block]
-        flat, views, send, sviews = None, {}, None, {}
-        layer_no = 1 if relu else 2
-        # the peer all-reduce: each relation-sharded group's sum goes to this rank's slot (and
-        # every peer's copy of it) from the epilogue launch; no flat buffer, no RCCL all-reduce
-        peer_red = self.peer_reduce and bool(red) and bool(split_t)
-        if peer_red:
+        split_t = [i for i in self.targets if i in self.row_block and i not in self.fused]
+        if split_t:
+            reduces = self._finish_blocks(L, lf, split_t, partials, sviews, reduces)
+        L.launches += reduces
+        if lf.peer_red:
+            # the relation-sharded rows finished from the world slots, added in rank order by
+            # the dense-rows groups of ONE fused launch (l2norm, Σ_j, relu, layer-1 projections)
+            self._finish_sums(L, lf, projs, self._slots_spec)
+        elif L.flat is not None:
+            # sharded: the all-reduced group sums S_ij are finished by ONE fused launch whose
+            # groups are the dense rows S_ij[r] themselves (DG_GROUP_DENSE_ROWS), so the l2norm,
+            # Σ_j, relu and (layer 1) the layer-2 projections of every node type run in one
+            # kernel after the exchange
+            self._finish_sums(L, lf, projs, lambda i, et, layer, d: self._identity_spec(i, L.views[et], d))
+        elif not split_t:
+            self._finish_plain(L, lf, rest, partials)
+        L.gather_all = self._peer_gather_all(L.gathers, layer)
+        return L
+
+    def _build_seg_rows(self, lf: LayerForms, xs, seg_w) -> "_Layer":
+        """Seg mode, every node type row-split: one launch finishes this rank's row block of each
+        (its workgroups' waves loop over the N relation sets), then the all-gathers."""
+        gathers, rows = [], {}
+        for i in self.targets:
+            pad, blk, rows[i] = self._row_block_of(i, lf.layer)
+            gathers.append((pad, blk))
+        tgts = self._seg_targets(rows, xs, seg_w, lf.relu)
+        peer = self._peer_fused(lf.layer)
+        if lf.table == "tab":
+            # (one wave per relation here: dealing the pairs of N = 2's 14-relation rows over
+            # 16 wave slots measured 16.45 / 23.04 µs a rank against 16.39 / 22.65, RCCL no-op /
+            # peer loopback, round 6)
+            launch = kernels.PreparedFusedTab(tgts, lf.d_in, lf.d, peer=peer, balance=False)  # (the wave-table form)
+        else:
+            launch = kernels.PreparedFusedSeg(tgts, lf.d_in, lf.d, peer=peer)
+        self.launch_groups[id(launch)] = [et for i in self.targets for et in self.targets[i]]
+        if peer is not None:
+            gathers = []  # the launch itself ends with the exchange
+        return _Layer(launches=[launch], allreduce=self.allreduce, gathers=gathers, allgather=self.allgather,
+                      gather_all=self._peer_gather_all(gathers, lf.layer))
+
+    def _build_fused_seg(self, L: "_Layer", lf: LayerForms, xs, seg_w, post) -> None:
+        """One GPU: every node type finished by one fused-seg launch, in its wave-table form
+        where decide_forms found it fits."""
+        d_in, d = lf.d_in, lf.d
+        tgts = self._seg_targets({i: self._outs[lf.layer][i] for i in self.fused}, xs, seg_w, lf.relu)
+        weighted = _tab_weighted(d_in, d) if self.tab_weighted else 0
+        if lf.table == "tab":
+            # the wave-table form: the same rows bitwise, fewer dependent loads a wave
+            # (post: layer 1 also projecting its rows onto layer 2's relations, L2_PREPROJECT)
+            pj = []
+            for et, W2 in post.items():
+                grp = self.g.groups[et]
+                pj.append(kernels.TabProjSpec(self.fused.index(et[1]), W2, self.proj[et], grp.n_rels,
+                                              None if grp.rel_map is None else grp.rel_map.cpu().numpy()))
+            launch = kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d), projs=pj,
+                                              share_proj=L2_PREPROJECT_SHARE, weighted=weighted)
+        elif lf.table == "narrow":
+            # layer 2 over the P stacks layer 1 made: layer 1's shape at half the width
+            launch = kernels.PreparedFusedTab(tgts, d_in, d, balance=_tab_balance(d_in, d), weighted=weighted)
+            self._l2_tab = _L2Tab(tgts, list(self.fused), launch)
+        else:
+            launch = kernels.PreparedFusedSeg(tgts, d_in, d)
+        L.launches.append(launch)
+        self.launch_groups[id(launch)] = [et for i in self.fused for et in self.targets[i]]
+
+    def _build_fused(self, L: "_Layer", lf: LayerForms, xs, projs) -> None:
+        """self.fused finished by one dg_gcn_fused_f32 launch."""
+        g, fused_t, d = self.g, self.fused, lf.d
+        # waves per group: small launches (latency-bound) split the densest row group's
+        # batches of 64 over up to two waves; big launches have parallelism to spare
+        avg = max(g.groups[et].nnz / max(1, g.groups[et].n_rows) for i in fused_t for et in self.targets[i])
+        max_groups = max(len(self.targets[i]) for i in fused_t)
+        rows = sum(g.groups[self.targets[i][0]].n_rows for i in fused_t)
+        # (row blocks of N relation sets — config S's weak scaling — have N times longer
+        # rows over 1/N of the rows: up to 16 waves per row there; measured at N = 8, rank
+        # 0's layer 1: 27.0 µs at 2 waves per group)
+        cap = 16 // max_groups if self.row_block else 2
+        wpg = 1 if rows >= 4096 else int(max(1, min(cap, 16 // max_groups, math.ceil(avg / 64.0))))
+        tgts = []
+        for i in fused_t:
+            out = self._outs[lf.layer][i]
+            if i in self.row_block:
+                # a row-split node type (sharded): this rank's block, finished in place in the
+                # padded output, then all-gathered
+                pad, blk, out = self._row_block_of(i, lf.layer)
+                L.gathers.append((pad, blk))
+            tgts.append((out, out.shape[0], [self._spec(et, xs[et], None, d) for et in self.targets[i]], lf.relu))
+        L.launches.append(kernels.PreparedFused(tgts, d, self._retarget(projs, fused_t), wpg))
+        self.launch_groups[id(L.launches[-1])] = [et for i in fused_t for et in self.targets[i]]
+
+    def _sum_buffers(self, L: "_Layer", lf: LayerForms, red: List[EdgeType]) -> Dict[EdgeType, torch.Tensor]:
+        """Where each relation-sharded (or, training, every) group of `red` writes this rank's
+        pre-normalisation sum: {et: tensor}, empty outside flat mode."""
+        sviews: Dict[EdgeType, torch.Tensor] = {}
+        if lf.peer_red:
+            # the peer all-reduce: each relation-sharded group's sum goes to this rank's slot (and
+            # every peer's copy of it) from the epilogue launch; no flat buffer, no RCCL all-reduce
             for et in red:
-                sviews[et] = self._red_slots[layer_no, et][self.shard.rank]
+                sviews[et] = self._red_slots[lf.layer, et][self.shard.rank]
         elif self.flat_mode and red:
             # flat (the reduced sums, read by the finishing launch and the backward) and, when
             # sharded, send (this rank's partial sums, written by its SpMM / reduces): the
             # all-reduce runs out of place, so the regions of groups without local relations
             # stay zero from allocation on — no per-step fill
-            sizes = [g.groups[et].n_rows * d for et in red]
-            flat = torch.zeros(int(sum(sizes)), **f32)
-            send = torch.zeros_like(flat) if self.allreduce is not None else flat
+            sizes = [self.g.groups[et].n_rows * lf.d for et in red]
+            L.flat = torch.zeros(int(sum(sizes)), **self._f32)
+            L.send = torch.zeros_like(L.flat) if self.allreduce is not None else L.flat
             off = 0
             for et, sz in zip(red, sizes):
-                views[et] = flat[off:off + sz]
-                sviews[et] = send[off:off + sz]
+                L.views[et] = L.flat[off:off + sz]
+                sviews[et] = L.send[off:off + sz]
                 off += sz
+            L.need_zero = L.send is L.flat and any(self.g.groups[et].n_rels == 0 for et in red)
+        return sviews
+
+    def _build_partial(self, L: "_Layer", lf: LayerForms, rest, xs, staged_proj, seg_w, sviews):
+        """The partial-mode launches of the groups in `rest` — seg, staged, spmm, in that order,
+        each in slices of DG_MAX_GROUPS — into chunk partials: ({et: (partials, chunks)}, the
+        reduces of multi-chunk groups into their sums)."""
+        g, d = self.g, lf.d
         partials, specs, staged, reduces, segs = {}, [], [], [], []
-        # outside seg mode: layer 2 reassociated (seg_w) and, in layer 1, the row-split groups of
-        # SEG_ROWS_L1 — both in dg_spmm_seg_f32
-        reassoc = (set(seg_w or {}) | (self.seg_l1 if relu else set())) if not self.seg_mode else set()
+        # outside seg mode: layer 2 reassociated (seg_w), in dg_spmm_seg_f32
+        reassoc = set(seg_w) if not self.seg_mode else set()
         for et in rest:
             grp = g.groups[et]
             cst = staged_chunk_starts(grp, d) if grp.staged else None
             n_out = ((len(cst) - 1 if cst is not None else -(-_staged_n(grp) // staged_out_chunk(grp, d)))
                      if grp.staged else grp.n_chunks)
             if et in reassoc:
-                n_out = self._seg_chunks(et)
-            if flat is not None and et in views and n_out == 1:
+                n_out = self._seg_layout(grp)[5]
+            if L.flat is not None and et in L.views and n_out == 1:
                 part = sviews[et]  # single chunk: the SpMM writes the group sum in place
             else:
-                part = torch.zeros((max(1, n_out), grp.n_rows, d), **f32)
-                if flat is not None and et in views and grp.n_rels:
+                part = torch.zeros((max(1, n_out), grp.n_rows, d), **self._f32)
+                if L.flat is not None and et in L.views and grp.n_rels:
                     reduces.append(kernels.PreparedEpilogue([(part, n_out)], sviews[et], grp.n_rows, d, 0))
             partials[et] = (part, max(1, n_out))
             if not grp.n_rels:
                 continue
             if grp.staged:
-                sp = (staged_proj or {}).get(et)
-                staged.append(kernels.StagedSpec(
-                    grp.layout, grp.staged_slab if grp.staged_slab is not None else grp.rel_map, xs.get(et), part, staged_out_chunk(grp, d), d, grp.K * grp.n_cols,
-                    slab_max=int(grp.rel_ids.max()), proj=sp, chunk_start=cst))
+                staged.append((et, kernels.StagedSpec(
+                    grp.layout, grp.staged_slab if grp.staged_slab is not None else grp.rel_map, xs.get(et), part,
+                    staged_out_chunk(grp, d), d, grp.K * grp.n_cols,
+                    slab_max=int(grp.rel_ids.max()), proj=staged_proj.get(et), chunk_start=cst)))
             elif self.seg_mode or et in reassoc:
-                if et in (seg_w or {}):  # layer 2 reassociated: H1_j and W2's stack
-                    segs.append(self._seg_spec(et, seg_w[et][0], part, seg_w[et][1]))
-                else:
-                    segs.append(self._seg_spec(et, xs[et], part))
+                segs.append((et, self._seg_spec(et, xs, seg_w, part)))
             else:
-                specs.append(self._spec(et, xs[et], part, d))
-        spmm_ets = [et for et in rest if g.groups[et].n_rels and not g.groups[et].staged
-                    and not (self.seg_mode or et in reassoc)]
-        seg_ets = [et for et in rest if g.groups[et].n_rels and not g.groups[et].staged
-                   and (self.seg_mode or et in reassoc)]
-        if segs:
-            d_in = self.h1 if seg_w else d
-            for s in range(0, len(segs), DG_MAX_GROUPS):
-                part = segs[s:s + DG_MAX_GROUPS]
-                if WAVE_TABLE and wavetable._tab_shape(d_in, d, part):
-                    launches.append(kernels.PreparedSegTab(part, d_in, d))  # (the wave-table form)
-                else:
-                    launches.append(kernels.PreparedSeg(part, d_in, d))
-                self.launch_groups[id(launches[-1])] = seg_ets[s:s + DG_MAX_GROUPS]
-        staged_ets = [et for et in rest if g.groups[et].n_rels and g.groups[et].staged]
-        for s in range(0, len(staged), DG_MAX_GROUPS):
-            launches.append(kernels.PreparedStaged(staged[s:s + DG_MAX_GROUPS], d))
-            self.launch_groups[id(launches[-1])] = staged_ets[s:s + DG_MAX_GROUPS]
-        for s in range(0, len(specs), DG_MAX_GROUPS):
-            launches.append(kernels.PreparedSpmm(specs[s:s + DG_MAX_GROUPS], d))
-            self.launch_groups[id(launches[-1])] = spmm_ets[s:s + DG_MAX_GROUPS]
-        need_zero = send is flat and flat is not None and any(g.groups[et].n_rels == 0 for et in red)
-        epis, local_epis = [], []
-        epi_peer = self._peer_fused(relu) if split_t else None
-        if split_t:
-            blocks = []
-            for i in split_t:
-                a, b, blk = self.row_block[i]
-                pad = self._pad[i, 1 if relu else 2]
-                r0 = self.shard.rank * blk
-                parts = [partials[et] for et in self.targets[i]]
-                if self.keep_sums:
-                    # training: the epilogue also keeps each group's pre-normalisation sum S_ij over
-                    # this rank's block rows (the backward's l2-norm gradient reads them)
-                    for n_, et in enumerate(self.targets[i]):
-                        views[et] = torch.empty((b - a) * d, **f32)
-                        parts[n_] = (parts[n_][0], parts[n_][1], views[et])
-                blocks.append((parts, pad[r0:r0 + (b - a)], b - a))
-                if epi_peer is None:  # (else the epilogue launch itself ends with the exchange)
-                    gathers.append((pad, pad[r0:r0 + blk]))
-            n_push = len(blocks)
-            # the relation-sharded node types' chunk reduces ride in the same launch: a target
-            # whose groups write their pre-normalisation sums into the send buffer (its
-            # finished rows go to a scratch buffer, unread) — one launch per layer instead of two
-            if peer_red:
-                # every relation-sharded group with local relations: its sum into this rank's
-                # slot, pushed to every peer (the rest of the slot stays zero)
-                red_t = [i for i in self.targets if i not in self.row_block
-                         and any(g.groups[et].n_rels for et in self.targets[i])]
-            else:
-                red_t = [i for i in self.targets if i not in self.row_block
-                         and any(et in views and g.groups[et].n_rels and partials[et][1] > 1
-                                 for et in self.targets[i])]
-            n_groups = sum(len(self.targets[i]) for i in split_t + red_t)
-            fits = len(split_t) + len(red_t) <= 8 and n_groups <= DG_MAX_GROUPS
-            # (__init__ enabled peer_red only where _peer_reduce_fits said these targets fit)
-            assert fits or not peer_red
-            if (reduces or peer_red) and fits:
-                for i in red_t:
-                    grp_parts = []
-                    for et in self.targets[i]:
-                        part, nc = partials[et][:2]
-                        if peer_red:
-                            grp_parts.append((part, nc, sviews[et] if g.groups[et].n_rels else None, True))
-                            continue
-                        reduced = et in views and g.groups[et].n_rels and nc > 1
-                        grp_parts.append((part, nc, sviews[et] if reduced else None))
-                    blocks.append((grp_parts, torch.empty((n[i], d), **f32), n[i]))
-                reduces = []
-            local_epis.append(_epilogue(blocks, d, flags, peer=epi_peer, push=[t < n_push for t in range(len(blocks))]))
-        launches += reduces
-        if peer_red:
-            # the relation-sharded rows finished from the world slots, added in rank order by
-            # the dense-rows groups of ONE fused launch (l2norm, Σ_j, relu, layer-1 projections)
-            tl = [i for i in self.targets if i not in self.row_block]
-            pspecs = []
-            for tgt_node, pj in projs:
-                pj.target = tl.index(tgt_node)
-                pspecs.append(pj)
+                specs.append((et, self._spec(et, xs[et], part, d)))
 
-            def slots_spec(i, et):
-                sl = self._red_slots[layer_no, et]
-                per = sl.stride(0)
-                x = torch.as_strided(self.xregion, ((self.world - 1) * per + n[i] * d,), (1,), sl.storage_offset())
-                return kernels.RelGroupSpec(None, None, None, x, None, n[i], self.world, d, per // d, dense=True)
+        def seg_launch(part):
+            if WAVE_TABLE and wavetable._tab_shape(lf.d_in, d, part):
+                return kernels.PreparedSegTab(part, lf.d_in, d)  # (the wave-table form)
+            return kernels.PreparedSeg(part, lf.d_in, d)
 
-            epis.append(kernels.PreparedFused(
-                [(outs[i], n[i], [slots_spec(i, et) for et in self.targets[i]], relu) for i in tl], d, pspecs, 1))
-        elif flat is not None:
-            # sharded: the all-reduced group sums S_ij are finished by ONE fused launch whose
-            # groups are the dense rows S_ij[r] themselves (DG_GROUP_DENSE_ROWS), so the l2norm,
-            # Σ_j, relu and (layer 1) the layer-2 projections of every node type run in one
-            # kernel after the exchange
-            tl = [i for i in self.targets if i not in self.row_block]
-            pspecs = []
-            for tgt_node, pj in projs:
-                pj.target = tl.index(tgt_node)
-                pspecs.append(pj)
-            epis.append(kernels.PreparedFused(
-                [(outs[i], n[i], [self._identity_spec(i, views[et], d) for et in self.targets[i]], relu)
-                 for i in tl], d, pspecs, 1))
-        elif not split_t:
-            if self.sums_mode:  # training: the epilogue also writes each group's S_ij
-                for et in rest:
-                    views[et] = torch.empty(g.groups[et].n_rows * d, **f32)
-                    partials[et] = partials[et] + (views[et],)
-            # every partial-mode node type finishes in ONE launch (side by side, no stream fork)
-            tl = [i for i in self.targets if i not in fused_t]
-            # node types with the most chunk partials per row first: their long rows start early
-            tl.sort(key=lambda i: -sum(partials[et][1] for et in self.targets[i]))
-            if tl:
-                epis.append(_epilogue([([partials[et] for et in self.targets[i]], outs[i], n[i]) for i in tl], d, flags))
-        return _Layer(launches, flat, need_zero, self.allreduce, epis, fused_t, views, self.side_stream, send,
-                      local_epis, gathers, self.allgather, self._peer_gather_all(gathers, relu))
+        for items, make in ((segs, seg_launch), (staged, lambda part: kernels.PreparedStaged(part, d)),
+                            (specs, lambda part: kernels.PreparedSpmm(part, d))):
+            for s in range(0, len(items), DG_MAX_GROUPS):
+                part = items[s:s + DG_MAX_GROUPS]
+                L.launches.append(make([spec for _, spec in part]))
+                self.launch_groups[id(L.launches[-1])] = [et for et, _ in part]
+        return partials, reduces
+
+    def _finish_blocks(self, L: "_Layer", lf: LayerForms, split_t, partials, sviews, reduces) -> list:
+        """The local epilogue: one launch finishes this rank's row block of every node type of
+        split_t before the exchange (pushing the rows itself with a fused peer exchange), the
+        chunk reduces — or the peer all-reduce's sums — riding along where they fit.  Returns
+        the reduces left to run as launches of their own."""
+        g, n, d = self.g, self.g.n_nodes, lf.d
+        epi_peer = self._peer_fused(lf.layer)
+        blocks = []
+        for i in split_t:
+            pad, blk, out = self._row_block_of(i, lf.layer)
+            parts = [partials[et] for et in self.targets[i]]
+            if self.keep_sums:
+                # training: the epilogue also keeps each group's pre-normalisation sum S_ij over
+                # this rank's block rows (the backward's l2-norm gradient reads them)
+                for n_, et in enumerate(self.targets[i]):
+                    L.views[et] = torch.empty(out.shape[0] * d, **self._f32)
+                    parts[n_] = (parts[n_][0], parts[n_][1], L.views[et])
+            blocks.append((parts, out, out.shape[0]))
+            if epi_peer is None:  # (else the epilogue launch itself ends with the exchange)
+                L.gathers.append((pad, blk))
+        n_push = len(blocks)
+        # the relation-sharded node types' chunk reduces ride in the same launch: a target
+        # whose groups write their pre-normalisation sums into the send buffer (its
+        # finished rows go to a scratch buffer, unread) — one launch per layer instead of two
+        # (the peer all-reduce: every relation-sharded group with local relations, its sum into
+        # this rank's slot, pushed to every peer — the rest of the slot stays zero; decide_forms
+        # turned it on only where these targets fit the launch)
+        def summed(et):
+            return bool(g.groups[et].n_rels) and (lf.peer_red or (et in L.views and partials[et][1] > 1))
+
+        red_t = [i for i in self.targets if i not in self.row_block and any(summed(et) for et in self.targets[i])]
+        if lf.peer_red or (reduces and _epilogue_fits(len(split_t) + len(red_t),
+                                                      sum(len(self.targets[i]) for i in split_t + red_t))):
+            for i in red_t:
+                grp_parts = [partials[et][:2] + (sviews[et] if summed(et) else None,) + ((True,) if lf.peer_red else ())
+                             for et in self.targets[i]]
+                blocks.append((grp_parts, torch.empty((n[i], d), **self._f32), n[i]))
+            reduces = []
+        flags = DG_EPI_L2NORM | (DG_EPI_RELU if lf.relu else 0)
+        L.local_epilogues.append(_epilogue(blocks, d, flags, peer=epi_peer,
+                                           push=[t < n_push for t in range(len(blocks))]))
+        return reduces
+
+    def _finish_sums(self, L: "_Layer", lf: LayerForms, projs, spec) -> None:
+        """The relation-sharded (or, training, all) node types finished from their groups' sums
+        by ONE fused launch over dense-rows groups; spec(i, et, layer, d) is a group's."""
+        n, tl = self.g.n_nodes, [i for i in self.targets if i not in self.row_block]
+        L.epilogues.append(kernels.PreparedFused(
+            [(self._outs[lf.layer][i], n[i], [spec(i, et, lf.layer, lf.d) for et in self.targets[i]], lf.relu)
+             for i in tl], lf.d, self._retarget(projs, tl), 1))
+
+    def _finish_plain(self, L: "_Layer", lf: LayerForms, rest, partials) -> None:
+        """One GPU: every partial-mode node type finishes in ONE epilogue launch (side by side,
+        no stream fork)."""
+        n, d = self.g.n_nodes, lf.d
+        if self.sums_mode:  # training: the epilogue also writes each group's S_ij
+            for et in rest:
+                L.views[et] = torch.empty(self.g.groups[et].n_rows * d, **self._f32)
+                partials[et] = partials[et] + (L.views[et],)
+        tl = [i for i in self.targets if i not in self.fused]
+        # node types with the most chunk partials per row first: their long rows start early
+        tl.sort(key=lambda i: -sum(partials[et][1] for et in self.targets[i]))
+        if tl:
+            flags = DG_EPI_L2NORM | (DG_EPI_RELU if lf.relu else 0)
+            L.epilogues.append(_epilogue([([partials[et] for et in self.targets[i]], self._outs[lf.layer][i], n[i])
+                                          for i in tl], d, flags))
 
     # ---- peer exchange (peer.py) ----
-    def _peer_reduce_fits(self, dgraph, split_nodes) -> bool:
-        """Whether the pushing epilogue launch can carry the peer all-reduce: the row-split node
-        types plus every relation-sharded node type with local relations as targets of ONE
-        dg_gcn_epilogue_peer_f32 launch (<= 8 targets, <= DG_MAX_GROUPS groups).  A larger graph
-        keeps the flat buffer and the RCCL all-reduce instead (it used to raise)."""
-        red_t = [i for i in self.targets if i not in self.row_block
-                 and any(dgraph.groups[et].n_rels for et in self.targets[i])]
-        t = list(split_nodes) + red_t
-        return len(t) <= 8 and sum(len(self.targets[i]) for i in t) <= DG_MAX_GROUPS
-
-    def _peer_fused(self, layer1: bool):
+    def _peer_fused(self, layer: int):
         """(PeerExchange, slot) for a finishing launch that pushes its rows and exchanges, or None."""
         if self.peer is None or self.peer.cfg.mode != "fused":
             return None
-        from .peer import SLOT_FUSED
+        return self.peer, SLOT_FUSED + layer - 1
 
-        return self.peer, SLOT_FUSED + (0 if layer1 else 1)
-
-    def _peer_gather_all(self, gathers, layer1: bool):
+    def _peer_gather_all(self, gathers, layer: int):
         """With a peer exchange, the layer's remaining all-gathers as ONE stand-alone
         dg_peer_allgather launch (mode "kernel", or a finishing launch without a push form)."""
         if self.peer is None or not gathers:
             return None
-        from .peer import SLOT_KERNEL
-
-        return self.peer.allgather_fn([blk for _, blk in gathers], SLOT_KERNEL + (0 if layer1 else 1))
+        return self.peer.allgather_fn([blk for _, blk in gathers], SLOT_KERNEL + layer - 1)
 
     def peer_probe(self):
         """bench.py: each layer's stand-alone peer exchange of this rank's blocks (slots
         SLOT_PROBE + layer - 1), to time beside whatever exchange the plan runs."""
-        from .peer import SLOT_PROBE
-
         out = []
         for layer in (1, 2):
-            blks = [self._pad[i, layer][self.shard.rank * self.row_block[i][2]:
-                                        (self.shard.rank + 1) * self.row_block[i][2]]
-                    for i in self.targets if i in self.row_block]
+            blks = [self._row_block_of(i, layer)[1] for i in self.targets if i in self.row_block]
             if blks:
                 out.append(self.peer.allgather_fn(blks, SLOT_PROBE + layer - 1))
         return out
+
+    def _slots_spec(self, i: int, et: EdgeType, layer: int, d: int) -> kernels.RelGroupSpec:
+        """The peer all-reduce's dense-rows group: the world slots of (layer, et) as chunks."""
+        sl = self._red_slots[layer, et]
+        per, n_i = sl.stride(0), self.g.n_nodes[i]
+        x = torch.as_strided(self.xregion, ((self.world - 1) * per + n_i * d,), (1,), sl.storage_offset())
+        return kernels.RelGroupSpec(None, None, None, x, None, n_i, self.world, d, per // d, dense=True)
 
     def _identity_spec(self, i: int, x: torch.Tensor, d: int) -> kernels.RelGroupSpec:
         """A group spec with no adjacency (DG_GROUP_DENSE_ROWS): the fused kernel reads the dense
@@ -1249,8 +1364,8 @@ class ForwardPlan:
         Only layer 2's table and launch are rebuilt; release_decoder_rows undoes it."""
         if not knob("DG_DEC_PREPROJECT", True):
             return None
-        tab = getattr(self, "_l2_tab", None)
-        if not self.preproj or tab is None or self.h2 != 32 or node_type not in tab[4]:
+        tab = self._l2_tab
+        if not self.preproj or tab is None or self.h2 != 32 or node_type not in tab.nodes:
             return None
         if (G.dtype != torch.float32 or tuple(G.shape) != (32, 32) or not G.is_contiguous() or G.data_ptr() % 16
                 or G.device != self.embeddings[node_type].device):
@@ -1264,12 +1379,12 @@ class ForwardPlan:
                 return None
             self._dec["users"] += 1
             return self._dec["Q"]
-        tgts, d_in, d, balance, fused_t, plain, weighted = tab
         E = self.embeddings[node_type]
         Q = torch.zeros((E.shape[0], 32), dtype=torch.float32, device=E.device)
-        launch = kernels.PreparedFusedTab(tgts, d_in, d, balance=balance, weighted=weighted,
-                                          dec=kernels.TabDecSpec(fused_t.index(node_type), G, l, Q))
-        self._swap_l2(plain, launch)
+        p = tab.plain
+        launch = kernels.PreparedFusedTab(tab.targets, p.d_in, p.d_out, balance=p.balance, weighted=p.weighted,
+                                          dec=kernels.TabDecSpec(tab.nodes.index(node_type), G, l, Q))
+        self._swap_l2(tab.plain, launch)
         self._dec = {"key": key, "Q": Q, "G": G, "l": l, "launch": launch, "users": 1, "runs": self.runs}
         return Q
 
@@ -1281,7 +1396,7 @@ class ForwardPlan:
         self._dec["users"] -= 1
         if self._dec["users"] > 0:
             return
-        self._swap_l2(self._dec["launch"], self._l2_tab[5])
+        self._swap_l2(self._dec["launch"], self._l2_tab.plain)
         # (kept alive with the plan: a graph captured while attached still replays that launch)
         self._dec_retired.append(self._dec)
         self._dec = None
@@ -1335,12 +1450,6 @@ class ForwardPlan:
         return pick(self._layer1), pick(self._layer2)
 
     # ---- accounting (bench / DESIGN.md roofline) ----
-    def _out_rows(self, i: int) -> int:
-        """Rows of node type i this plan finishes (a row-split rank: its block)."""
-        if i in self.row_block:
-            return self.row_block[i][1] - self.row_block[i][0]
-        return self.g.n_nodes[i]
-
     def group_bytes(self, et: EdgeType, d: int, fused: bool, layer: int = 1) -> int:
         """Algorithmic bytes of one group's SpMM: its CSR once (4 B per row of each
         relation + 8 B per nonzero), its dense operands once (4·d B per row of each X_k) and,
@@ -1355,6 +1464,18 @@ class ForwardPlan:
             tot += 4 * d * grp.n_cols * grp.n_rels
         return tot if fused else tot + 4 * d * grp.n_rows
 
+    def _extra_bytes(self, launch, layer: int) -> int:
+        """What a launch moves beside its groups and rows: layer 1, W2 slabs read once and P rows
+        written once by its projections (PreparedFused's epilogue, PreparedFusedTab's jobs);
+        layer 2, G / l read once and Q rows written once where it makes the decoder's operands."""
+        if layer == 1:
+            return sum(4 * pj.n_rels * (pj.w.shape[1] * pj.w.shape[2] + pj.out.shape[1] * pj.w.shape[2])
+                       for pj in getattr(launch, "projs", ()))
+        dec = getattr(launch, "dec", None)
+        if dec is None:
+            return 0
+        return 4 * (dec.G.numel() + (dec.l.numel() if dec.l is not None else 0) + dec.out.numel())
+
     def launch_bytes(self, launch, layer: int) -> int:
         """Algorithmic bytes of one SpMM launch of a layer (its groups; a fused launch also
         writes its targets' rows once, and in layer 1 reads W2 / writes P for its fused
@@ -1365,34 +1486,8 @@ class ForwardPlan:
         fused = isinstance(launch, (kernels.PreparedFused, kernels.PreparedFusedSeg))
         tot = sum(self.group_bytes(et, d, fused, layer) for et in ets)
         if fused:
-            tot += sum(4 * d * self._out_rows(i) for i in L.fused_targets)
-            if layer == 1 and isinstance(launch, kernels.PreparedFused):
-                for pj in launch._keep[2]:
-                    K, din, dout = pj.w.shape
-                    tot += 4 * pj.n_rels * (din * dout + pj.out.shape[1] * dout)
-            if layer == 1:
-                tot += self._post_bytes(launch)
-            else:
-                tot += self._dec_bytes(launch)
+            tot += sum(4 * d * _local_rows(self.g, i) for i in L.fused_targets) + self._extra_bytes(launch, layer)
         return tot
-
-    @staticmethod
-    def _post_bytes(launch) -> int:
-        """W2 slabs read once and P rows written once by a projecting layer-1 launch."""
-        tot = 0
-        for pj in getattr(launch, "projs", ()):
-            K, din, dout = pj.w.shape
-            tot += 4 * pj.n_rels * (din * dout + pj.out.shape[1] * dout)
-        return tot
-
-    @staticmethod
-    def _dec_bytes(launch) -> int:
-        """G / l read once and Q rows written once by a layer-2 launch that makes the decoder's
-        row operands."""
-        dec = getattr(launch, "dec", None)
-        if dec is None:
-            return 0
-        return 4 * (dec.G.numel() + (dec.l.numel() if dec.l is not None else 0) + dec.out.numel())
 
     def layer_bytes(self, layer: int) -> int:
         """Algorithmic (compulsory) HBM bytes of one layer's SpMM launches: the CSR once
@@ -1403,51 +1498,27 @@ class ForwardPlan:
         projections' W2 reads and P writes."""
         L = self._layer1 if layer == 1 else self._layer2
         d = self.h1 if layer == 1 else self.h2
-        tot = 0
-        for et, grp in self.g.groups.items():
-            if not grp.n_rels:
-                continue
-            tot += 4 * (grp.n_rels * grp.n_rows + 1) + 8 * grp.nnz
-            if layer == 2 and (et in self.staged_proj or et in self.seg_proj):  # H1_j and W2 instead of P_k
-                tot += 4 * self.h1 * (grp.n_cols + d * grp.n_rels)
-            else:
-                tot += 4 * d * grp.n_cols * grp.n_rels
-            if et[0] not in L.fused_targets:
-                tot += 4 * d * grp.n_rows
-        for i in L.fused_targets:
-            tot += 4 * d * self._out_rows(i)
-        if layer == 1:
-            for f in L.launches:
-                if isinstance(f, kernels.PreparedFused):
-                    for pj in f._keep[2]:
-                        K, din, dout = pj.w.shape
-                        rows = pj.out.shape[1]
-                        tot += 4 * pj.n_rels * (din * dout + rows * dout)
-                tot += self._post_bytes(f)
-        else:
-            for f in L.launches:
-                tot += self._dec_bytes(f)
-        return tot
+        tot = sum(self.group_bytes(et, d, et[0] in L.fused_targets, layer) for et in self.g.groups)
+        tot += sum(4 * d * _local_rows(self.g, i) for i in L.fused_targets)
+        return tot + sum(self._extra_bytes(f, layer) for f in L.launches)
 
 
+@dataclass
 class _Layer:
     """The prepared launches of one layer and how to run them."""
 
-    def __init__(self, launches, flat, need_zero, allreduce, epilogues, fused_targets, views=None,
-                 side_stream=None, send=None, local_epilogues=(), gathers=(), allgather=None, gather_all=None):
-        self.launches = launches
-        self.side_stream = side_stream
-        self.flat = flat
-        self.send = flat if send is None else send  # this rank's partial sums (sharded: all-reduced into flat)
-        self.views = views or {}  # flat mode: (i,j) -> that group's S_ij, [n_i * d]
-        self.need_zero = need_zero
-        self.allreduce = allreduce
-        self.epilogues = epilogues
-        self.fused_targets = fused_targets
-        self.local_epilogues = list(local_epilogues)  # row-split blocks, finished before the exchange
-        self.gathers = list(gathers)                  # (padded out, this rank's block) per node type
-        self.allgather = allgather
-        self.gather_all = gather_all                  # all gathers in one peer-exchange launch
+    launches: List[Callable[[], None]] = field(default_factory=list)
+    flat: Optional[torch.Tensor] = None   # flat mode: the (reduced) sums of every group, one buffer
+    send: Optional[torch.Tensor] = None   # this rank's partial sums (sharded: all-reduced into flat)
+    views: Dict[EdgeType, torch.Tensor] = field(default_factory=dict)  # (i,j) -> that group's S_ij, [n_i * d]
+    need_zero: bool = False
+    allreduce: Optional[Callable[..., None]] = None
+    epilogues: List[Callable[[], None]] = field(default_factory=list)
+    fused_targets: Sequence[int] = ()
+    local_epilogues: List[Callable[[], None]] = field(default_factory=list)  # row-split blocks, finished before the exchange
+    gathers: list = field(default_factory=list)  # (padded out, this rank's block) per node type
+    allgather: Optional[Callable[..., None]] = None
+    gather_all: Optional[Callable[[], None]] = None  # all gathers in one peer-exchange launch
 
     @property
     def has_exchange(self) -> bool:
@@ -1476,30 +1547,7 @@ class _Layer:
             e()
 
     def run_spmm(self) -> None:
-        """The layer's SpMM launches (and chunk reduces), as the forward runs them."""
-        side = [l for l in self.launches if isinstance(l, kernels.PreparedSpmm)]
-        main = [l for l in self.launches if not isinstance(l, kernels.PreparedSpmm)]
-        if (self.side_stream is not None and side
-                and any(isinstance(l, kernels.PreparedStaged) for l in main)):
-            # fork: the gather-bound launches on the side stream, the LDS-bound staged ones
-            # here; join before the chunk reduces / epilogues (graph-capturable)
-            cur = torch.cuda.current_stream()
-            self.side_stream.wait_stream(cur)
-            if STAGED_FIRST:  # the LDS-full staged workgroups claim their CUs first
-                for l in main:
-                    if not isinstance(l, kernels.PreparedEpilogue):
-                        l()
-            with torch.cuda.stream(self.side_stream):
-                for l in side:
-                    l()
-            if not STAGED_FIRST:
-                for l in main:
-                    if not isinstance(l, kernels.PreparedEpilogue):
-                        l()
-            cur.wait_stream(self.side_stream)
-            for l in main:
-                if isinstance(l, kernels.PreparedEpilogue):
-                    l()
-        else:
-            for l in self.launches:
-                l()
+        """The layer's SpMM launches (and chunk reduces), as the forward runs them: in order,
+        on one stream."""
+        for l in self.launches:
+            l()

@@ -21,8 +21,6 @@ from . import _lib, wavetable
 from .tuning import knob
 from ._lib import (DgAdamSeg, DgEpiGroup, DgFusedTarget, DgGemmDesc, DgL2gGroup, DgProj, DgRelGroup,
                    DgStagedGroup, DgStagedProj, check)
-# the table helpers that callers found here before wavetable.py existed
-from .wavetable import _balanced_waves, _proj_jobs, _tab_geometry, tab_proj_fit  # noqa: F401
 
 
 def _stream_ptr(stream: Optional[torch.cuda.Stream] = None) -> int:
@@ -571,7 +569,8 @@ class PreparedFused:
         garr = (DgRelGroup * len(specs))()
         for i, s in enumerate(specs):
             _fill_group(garr[i], s)
-        self._keep = (specs, [t[0] for t in targets], list(projs))
+        self.projs = list(projs)
+        self._keep = (specs, [t[0] for t in targets], self.projs)
         self._garr, self._tarr, self._parr = garr, tarr, parr
         self._ng, self._nt, self._np, self.d = len(specs), len(targets), len(projs), d
         self.wpg = waves_per_group

@@ -2,7 +2,7 @@
 # REPS rounds (default 2), one summary line per run (scripts/bench_summary.py).
 # A variant is NAME — decagon_amd/lib/var_NAME.so, built on the CPU container with
 # `python -m decagon_amd._build NAME FLAG[=VALUE]...` — or VAR=value, an environment setting (knobs
-# such as DG_S_ROWS_FORM, DG_PROJ_BLOCKS, DG_WPG; several joined by commas) with the default library,
+# such as DG_S_ROWS_FORM, DG_PROJ_BLOCKS, DG_TAB_BALANCE; several joined by commas) with the default library,
 # or NAME@VAR=value[,VAR=value], both.
 # Usage: bash scripts/ab.sh <tag> "<bench args>" VARIANT...
 set -o pipefail
