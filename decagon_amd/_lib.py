@@ -311,6 +311,15 @@ SIGNATURES = {
     "dg_rank_metrics_seg_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                           c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     "dg_seg_tile_lookup": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    "dg_decoder_score_cross_f32": (
+        c_int32,
+        [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int64,
+         c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p],
+    ),
+    "dg_decoder_score_cross_chunk": (c_int32, [c_int32, c_int32]),
+    "dg_row_topk_workspace": (c_int64, [c_int32, c_int32, c_int32]),
+    "dg_row_topk_f32": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int64, c_void_p]),
     "dg_unigram_sample_slots": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, ctypes.c_uint64,
                                           c_void_p, c_void_p]),
     "dg_unigram_sample": (

@@ -97,6 +97,25 @@ __device__ unsigned long long g_dec_prof[256][2][kDecProfSlots];
 #define DG_DEC_STAMP(i) ((void)0)
 #endif
 
+// Reduce-scatter of 16 per-lane partials over the 32 lanes of each half-wave: at each step a lane
+// keeps the half of its remaining scores that its lane bit selects and adds its partner's copy
+// of them.  Returns score r = (lane & 31) >> 1 of the half (lanes 2r and 2r + 1 hold the same
+// value).  The tree has the same shape for every score, so a score does not depend on its slot.
+__device__ __forceinline__ float reduce_scatter32(const float (&part)[16]) {
+    const int i = threadIdx.x & 31;
+    const int b4 = (i >> 4) & 1, b3 = (i >> 3) & 1, b2 = (i >> 2) & 1, b1 = (i >> 1) & 1;
+    float v8[8], v4[4], v2[2];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        v8[j] = (b4 ? part[8 + j] : part[j]) + xor_get<16>(b4 ? part[j] : part[8 + j]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v4[j] = (b3 ? v8[4 + j] : v8[j]) + xor_get<8>(b3 ? v8[j] : v8[4 + j]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) v2[j] = (b2 ? v4[2 + j] : v4[j]) + __shfl_xor(b2 ? v4[j] : v4[2 + j], 4);
+    float v1 = (b1 ? v2[1] : v2[0]) + xor_get<2>(b1 ? v2[0] : v2[1]);
+    return xor_add<1>(v1);  // score r = 8·b4 + 4·b3 + 2·b2 + b1 = (lane & 31) >> 1
+}
+
 template <bool kSc1 = false, int kD = 0>
 __device__ __forceinline__ void score_tile(const DecTab& t, int ridx, int cidx, bool valid,
                                            float (&part)[16]) {
@@ -193,20 +212,7 @@ __device__ __forceinline__ void score_tile(const DecTab& t, int ridx, int cidx, 
 #pragma unroll
         for (int r = 0; r < 16; ++r) part[r] = fmaf(acc[r] * lj, v[r], part[r]);
     }
-    // reduce-scatter over the half's 32 lanes: at each step a lane keeps the half of its
-    // remaining scores that its lane bit selects and adds its partner's copy of them
-    const int b4 = (i >> 4) & 1, b3 = (i >> 3) & 1, b2 = (i >> 2) & 1, b1 = (i >> 1) & 1;
-    float v8[8], v4[4], v2[2];
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-        v8[j] = (b4 ? part[8 + j] : part[j]) + xor_get<16>(b4 ? part[j] : part[8 + j]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v4[j] = (b3 ? v8[4 + j] : v8[j]) + xor_get<8>(b3 ? v8[j] : v8[4 + j]);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) v2[j] = (b2 ? v4[2 + j] : v4[j]) + __shfl_xor(b2 ? v4[j] : v4[2 + j], 4);
-    float v1 = (b1 ? v2[1] : v2[0]) + xor_get<2>(b1 ? v2[0] : v2[1]);
-    v1 = xor_add<1>(v1);
-    part[0] = v1;  // score r = 8·b4 + 4·b3 + 2·b2 + b1 = (lane & 31) >> 1
+    part[0] = reduce_scatter32(part);
     DG_DEC_STAMP(4);  // reduce-scatter
 }
 

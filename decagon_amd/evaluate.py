@@ -24,6 +24,11 @@ an edge type — the reference's loop over edge_type2idx, DecagonAccuracyEvaluat
 in one pass: the sampled pairs of all relations packed into segments (pack_edge_samples), one
 scorer launch (dg_decoder_score_seg_f32) and one segmented metrics call
 (dg_rank_metrics_seg_f32), row for row the bits of the per-relation call.
+
+pair_profiles and top_relations answer the query the other way round — for given node pairs, the
+score of every relation of the edge type and each pair's best relations (NpPredictor._predictEdges
+per relation id, main/Predictor/NpPredictor.py:293-313): one launch over pairs × relations
+(dg_decoder_score_cross_f32) and a per-pair selection on the device (dg_row_topk_f32).
 """
 from __future__ import annotations
 
@@ -339,3 +344,101 @@ def accuracy_scores_all(sess, opt, placeholders, feed_dict, edges_pos, edges_neg
     if not pooled:
         return res
     return res[:-1], (float(res[-1, 0]), float(res[-1, 1]))
+
+
+def _profile_query(name, sess, opt, placeholders, feed_dict, pairs, edge_type_ij, relations, sigmoid, run):
+    """The part pair_profiles and top_relations share: checks, one sess.run at dropout 0 of a Node
+    that uploads [row_idx | col_idx | rel_idx] once and returns run(row_t, col_t, ri, ci, G, l, rel_idx)."""
+    if sigmoid not in SIGMOID_MODES:
+        raise ValueError(f"sigmoid must be one of {list(SIGMOID_MODES)}")
+    i, j = edge_type_ij
+    model = opt._model()
+    if (i, j) not in model.edge_type2decoder:
+        raise ValueError(f"unknown edge type {(i, j)}")
+    dec = model.edge_type2decoder[i, j]
+    K = dec.num_types
+    pr = np.asarray(pairs, dtype=np.int64)
+    if pr.ndim != 2 or pr.shape[1] != 2:
+        raise ValueError("pairs must be an [n, 2] array")
+    rels = np.arange(K, dtype=np.int64) if relations is None else np.asarray(relations, np.int64).reshape(-1)
+    if rels.size < 1:
+        raise ValueError("no relations to score")
+    if rels.min() < 0 or rels.max() >= K:
+        raise ValueError(f"relation outside [0, {K})")
+    fd = dict(feed_dict)
+    fd[placeholders["dropout"]] = 0.0
+
+    def fn(ctx: RunContext):
+        ets = list(model.edge_types)
+        first = sum(model.edge_types[et] for et in ets[:ets.index((i, j))])  # flat index of relation 0
+        for r in range(first, first + K):
+            if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
+                raise ValueError(f"{name} reads the decoder's variables; a latent matrix is fed")
+        row_t, col_t = opt._tables(ctx, i, j)
+        if pr.size and (pr.min() < 0 or pr[:, 0].max() >= row_t.shape[0] or pr[:, 1].max() >= col_t.shape[0]):
+            raise ValueError("pair outside the embedding tables")
+        G, l = _stacked_latents(ctx, dec, row_t.shape[1])
+        n = pr.shape[0]
+        host = np.concatenate([pr[:, 0], pr[:, 1], rels]).astype(np.int32)
+        buf = torch.from_numpy(host).to(ctx.session.device)
+        return run(row_t, col_t, buf[:n], buf[n:2 * n], G, l, buf[2 * n:])
+
+    return sess.run(Node(f"evaluate/{name}", fn), feed_dict=fd), rels
+
+
+def pair_profiles(sess, opt, placeholders, feed_dict, pairs, edge_type_ij, relations=None,
+                  sigmoid: Optional[str] = None) -> np.ndarray:
+    """The profile of node pairs: numpy [P, n_sel], entry [p, s] the score of relation
+    relations[s] (default: every relation of edge type (i, j), in order; repeats allowed) for
+    pair pairs[p] = (row node, column node).
+
+    What the reference gets from NpPredictor(relationId)._predictEdges
+    (main/Predictor/NpPredictor.py:293-313: E·D·R·D·Eᵀ of one relation, then the wanted entries)
+    run per relation id, and from the per-relation session.run(predictions) of
+    DecagonAccuracyEvaluator._computePredictions — here one sess.run at dropout 0, one upload of
+    the indices, one launch over pairs × relations (dg_decoder_score_cross_f32) and one copy back.
+    The decoder's variables are read in place for all four decoder types, so a fed latent matrix
+    is refused, as in top_candidates.  `pairs` is checked on the host against the table sizes
+    (ValueError).  `sigmoid` (a key of SIGMOID_MODES) transforms the returned logits."""
+    def run(row_t, col_t, ri, ci, G, l, rel):
+        return kernels.decoder_score_cross(row_t, col_t, ri, ci, G, l, rel_idx=rel)
+
+    res, _ = _profile_query("pair_profiles", sess, opt, placeholders, feed_dict, pairs, edge_type_ij, relations,
+                            sigmoid, run)
+    return _sigmoid_host(np.asarray(res), sigmoid)
+
+
+def top_relations(sess, opt, placeholders, feed_dict, pairs, edge_type_ij, k: int, relations=None,
+                  sigmoid: Optional[str] = None):
+    """For every pair its k highest-scoring relations of edge type (i, j) — "for this pair of
+    drugs, which side effects?": numpy (scores [P, k], relations [P, k] int32, counts [P] int32),
+    descending; slots past counts[p] hold −inf / −1.
+
+    Replaces the same reference paths as pair_profiles (NpPredictor.py:293-313 run per relation
+    id; the per-relation session.run(predictions) of DecagonAccuracyEvaluator._computePredictions)
+    followed by a sort of each pair's row on the host: here the pairs are scored in chunks and
+    each chunk selected on the device (kernels.decoder_top_relations), so no P×K matrix is formed
+    or copied.  `relations` restricts and orders the candidates (default: all, in order); the
+    returned array holds relation numbers, not positions.
+
+    The ranking is by LOGIT, ties by the earlier position in `relations`; `sigmoid` (a key of
+    SIGMOID_MODES) only transforms the returned scores, as in top_candidates."""
+    k = int(k)
+
+    def run(row_t, col_t, ri, ci, G, l, rel):
+        s, idx, n = kernels.decoder_top_relations(row_t, col_t, ri, ci, G, l, k, rel_idx=rel)
+        return torch.cat([s.view(torch.int32).reshape(-1), idx.reshape(-1), n])  # one copy back
+
+    flat, rels = _profile_query("top_relations", sess, opt, placeholders, feed_dict, pairs, edge_type_ij,
+                                relations, sigmoid, run)
+    flat = np.asarray(flat, np.int32)
+    P = flat.size // (2 * int(k) + 1)
+    s = flat[:P * k].view(np.float32).reshape(P, k)
+    idx, n = flat[P * k:2 * P * k].reshape(P, k), flat[2 * P * k:]
+    rel = np.where(idx >= 0, rels.astype(np.int32)[np.maximum(idx, 0)], np.int32(-1)).astype(np.int32)
+    if sigmoid is not None:
+        valid = np.arange(s.shape[1])[None, :] < n[:, None]
+        out = np.full(s.shape, -np.inf, np.float64 if sigmoid == "main" else np.float32)
+        out[valid] = _sigmoid_host(s[valid], sigmoid)
+        s = out
+    return s, rel, n

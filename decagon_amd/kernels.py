@@ -1283,6 +1283,191 @@ def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tens
     return scores, rows, cols, counts
 
 
+def cross_slot_chunk(n_pairs: int, n_sel: int) -> int:
+    """The slot chunk C dg_decoder_score_cross_f32 uses for n_pairs pairs against n_sel slots (one
+    wave scores a 32-pair tile against C consecutive slots): the library's own choice, host only."""
+    return int(_lib.load().dg_decoder_score_cross_chunk(int(n_pairs), int(n_sel)))
+
+
+def _cross_operands(name, row_table, col_table, row_idx, col_idx, G, l, rel_idx):
+    """Validation shared by decoder_score_cross and decoder_top_relations, in decoder_score_seg's
+    order (type, dtype, contiguity, shapes): (d, n_rows, n_cols, n_pairs, n_sel, n_rel)."""
+    tabs = [(row_table, "row_table"), (col_table, "col_table"), (G, "G")] + ([(l, "l")] if l is not None else [])
+    idx = [(row_idx, "row_idx"), (col_idx, "col_idx")] + ([(rel_idx, "rel_idx")] if rel_idx is not None else [])
+    for ts, dt in ((tabs, torch.float32), (idx, torch.int32)):
+        for t, nm in ts:
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{nm}: expected a torch.Tensor, got {type(t).__name__}")
+            if t.dtype != dt:
+                raise TypeError(f"{nm}: dtype {t.dtype}, expected {dt}")
+            if not t.is_contiguous():
+                raise ValueError(f"{nm}: must be contiguous")
+    if row_table.dim() != 2 or col_table.dim() != 2 or G.dim() not in (2, 3):
+        raise ValueError(f"{name}: tables must be [N, d] and G [d, d] or [K, d, d]")
+    d = G.shape[-1]
+    if G.shape[-2] != d or row_table.shape[1] != d or col_table.shape[1] != d:
+        raise ValueError(f"{name}: d mismatch")
+    if l is not None and (l.dim() not in (1, 2) or l.shape[-1] != d):
+        raise ValueError(f"{name}: d mismatch (l must be [d] or [K, d])")
+    if d not in (32, 64):
+        raise ValueError(f"{name}: d = {d} unsupported (32 or 64)")
+    n_rows, n_cols = row_table.shape[0], col_table.shape[0]
+    if n_rows < 1 or n_cols < 1:
+        raise ValueError(f"{name}: empty table")
+    if row_idx.dim() != 1 or col_idx.dim() != 1 or col_idx.numel() != row_idx.numel():
+        raise ValueError(f"{name}: row_idx / col_idx must be vectors of one length")
+    if rel_idx is not None and (rel_idx.dim() != 1 or rel_idx.numel() < 1):
+        raise ValueError(f"{name}: rel_idx must be a non-empty vector")
+    ks = {int(t.shape[0]) for t, per in ((G, G.dim() == 3), (l, l is not None and l.dim() == 2)) if per}
+    if len(ks) > 1:
+        raise ValueError(f"{name}: relation counts disagree: {sorted(ks)}")
+    K = ks.pop() if ks else None  # None: no per-relation operand, any relation index serves
+    if K is not None and K < 1:
+        raise ValueError(f"{name}: no relations")
+    if rel_idx is None and K is None:
+        raise ValueError(f"{name}: no per-relation operand: pass rel_idx to name the slots")
+    n_sel = rel_idx.numel() if rel_idx is not None else K
+    n_rel = K if K is not None else 2**31 - 1
+    return d, n_rows, n_cols, row_idx.numel(), n_sel, n_rel
+
+
+def _need_device(pairs) -> None:
+    for t, nm in pairs:
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{nm}: must be a device (HIP) tensor")
+
+
+def _score_cross_call(row_table, col_table, row_idx, col_idx, G, l, rel_idx, dims, p0, n, out, stream) -> None:
+    """Pairs [p0, p0 + n) into the rows of `out` (row stride out.stride(0)); arguments validated."""
+    d, n_rows, n_cols, _, n_sel, n_rel = dims
+    if n == 0:
+        return
+    check(_lib.load().dg_decoder_score_cross_f32(
+        row_table.data_ptr(), d, n_rows, col_table.data_ptr(), d, n_cols, row_idx.data_ptr() + 4 * p0,
+        col_idx.data_ptr() + 4 * p0, n, G.data_ptr(), d * d if G.dim() == 3 else 0,
+        l.data_ptr() if l is not None else None, d if (l is not None and l.dim() == 2) else 0,
+        rel_idx.data_ptr() if rel_idx is not None else None, n_sel, n_rel, d, out.data_ptr(), out.stride(0),
+        _stream_ptr(stream)), "dg_decoder_score_cross_f32")
+
+
+def decoder_score_cross(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: torch.Tensor,
+                        col_idx: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor],
+                        rel_idx: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                        stream=None) -> torch.Tensor:
+    """Every relation's score of every given pair in one launch (dg_decoder_score_cross_f32): a
+    float32 device tensor [P, n_sel],
+        out[p, s] = (row_table[row_idx[p]] ∘ l_k)ᵀ · G_k · (l_k ∘ col_table[col_idx[p]]),  k = rel_idx[s]
+    (rel_idx None: k = s, every relation in order) — bit for bit decoder_score(…, G_k, l_k) on
+    the same pairs.  Asynchronous; nothing is read on the host.
+
+    G: [d, d] (shared by every relation) or [K, d, d]; l: None (identity), [d] (shared) or [K, d];
+    K is the leading dimension of whichever is per relation; d is 32 or 64.  rel_idx: device int32
+    [n_sel] with values in [0, K), repeats and any order allowed (required when no operand is per
+    relation).  out: float32 [P, ≥ n_sel] device tensor or row-strided view (stride(1) == 1,
+    stride(0) ≥ n_sel); its columns past n_sel are not written, and out[:, :n_sel] is returned.
+    A pair outside the tables scores a row of NaN, a slot whose relation is outside [0, K) a
+    column of NaN."""
+    dims = _cross_operands("decoder_score_cross", row_table, col_table, row_idx, col_idx, G, l, rel_idx)
+    n, n_sel = dims[3], dims[4]
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+            raise TypeError("out: expected a float32 torch.Tensor")
+        if out.dim() != 2 or out.shape[0] != n or out.shape[1] < n_sel:
+            raise ValueError("decoder_score_cross: out must be [P, >= n_sel]")
+        if out.stride(1) != 1 or out.stride(0) < max(n_sel, out.shape[1]):
+            raise ValueError("decoder_score_cross: out must have stride(1) == 1 and stride(0) >= n_sel")
+    _need_device([(row_table, "row_table"), (col_table, "col_table"), (G, "G"), (l, "l"), (row_idx, "row_idx"),
+                  (col_idx, "col_idx"), (rel_idx, "rel_idx"), (out, "out")])
+    if n * (out.stride(0) if out is not None else n_sel) >= 2**38:
+        raise ValueError("decoder_score_cross: P·ld_out must stay below 2^38 (score in chunks of pairs)")
+    if out is None:
+        out = torch.empty((n, n_sel), device=G.device, dtype=torch.float32)
+    _score_cross_call(row_table, col_table, row_idx, col_idx, G, l, rel_idx, dims, 0, n, out, stream)
+    return out[:, :n_sel]
+
+
+def row_topk(x: torch.Tensor, topk: int, stream=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(values [n, topk] float32, idx [n, topk] int32, counts [n] int32): the topk highest entries
+    of every row of the float32 device matrix x, descending (dg_row_topk_f32: higher value first,
+    ties by smaller column, −0 as +0; counts = min(topk, columns), slots past it hold −inf / −1).
+    x may be a row-strided view (stride(1) == 1).  Asynchronous."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"x: expected a torch.Tensor, got {type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"x: dtype {x.dtype}, expected {torch.float32}")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError("row_topk: x must be [n, columns >= 1]")
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        raise ValueError("row_topk: x must have stride(1) == 1 and stride(0) >= its columns")
+    topk = int(topk)
+    if not 1 <= topk <= _lib.DG_TOPK_MAX_K:
+        raise ValueError(f"row_topk: topk must be in [1, {_lib.DG_TOPK_MAX_K}]")
+    if not x.is_cuda:
+        raise ValueError("x: must be a device (HIP) tensor")
+    n = x.shape[0]
+    vals = torch.empty((n, topk), dtype=torch.float32, device=x.device)
+    idx = torch.empty((n, topk), dtype=torch.int32, device=x.device)
+    counts = torch.empty(n, dtype=torch.int32, device=x.device)
+    _row_topk_call(x, topk, vals, idx, counts, stream)
+    return vals, idx, counts
+
+
+def _row_topk_call(x, topk, vals, idx, counts, stream) -> None:
+    n = x.shape[0]
+    if n == 0:
+        return
+    check(_lib.load().dg_row_topk_f32(x.data_ptr(), max(x.stride(0), x.shape[1]), n, x.shape[1], topk,
+                                      vals.data_ptr(), idx.data_ptr(), counts.data_ptr(), None, 0,
+                                      _stream_ptr(stream)), "dg_row_topk_f32")
+
+
+def top_relations_chunks(n_pairs: int, n_sel: int, max_workspace_bytes: int):
+    """The pair ranges [(start, stop), …] decoder_top_relations scores one after the other: every
+    range but the last holds the same number of pairs, a multiple of 32 and at least 32, and the
+    largest such number whose [pairs, n_sel] float32 score workspace fits max_workspace_bytes (32
+    pairs when not even those fit).  Pure host arithmetic."""
+    n_pairs, n_sel = int(n_pairs), int(n_sel)
+    if n_pairs < 0 or n_sel < 1:
+        raise ValueError("top_relations_chunks: needs n_pairs >= 0 and n_sel >= 1")
+    rows = max(32, int(max_workspace_bytes) // (4 * n_sel) // 32 * 32)
+    rows = min(rows, max(32, -(-n_pairs // 32) * 32))
+    return [(p, min(p + rows, n_pairs)) for p in range(0, n_pairs, rows)]
+
+
+def decoder_top_relations(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: torch.Tensor,
+                          col_idx: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor], topk: int,
+                          rel_idx: Optional[torch.Tensor] = None, max_workspace_bytes: int = 64 << 20,
+                          stream=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(scores [P, topk] float32, slots [P, topk] int32, counts [P] int32): for every pair the topk
+    highest-scoring slots of decoder_score_cross's row (operands and rel_idx as there; a slot is a
+    position of rel_idx, or the relation itself when rel_idx is None), in row_topk's order.
+
+    The pairs are scored top_relations_chunks(…) at a time into one [chunk, n_sel] workspace of at
+    most max_workspace_bytes (at least 32 rows) and each chunk is selected into its rows of the
+    outputs, so no P×n_sel matrix exists at any time.  A pair's scores do not depend on its
+    neighbours and the selection order is total: the result is the same, bytes and all, whatever
+    the bound."""
+    dims = _cross_operands("decoder_top_relations", row_table, col_table, row_idx, col_idx, G, l, rel_idx)
+    n, n_sel = dims[3], dims[4]
+    topk = int(topk)
+    if not 1 <= topk <= _lib.DG_TOPK_MAX_K:
+        raise ValueError(f"decoder_top_relations: topk must be in [1, {_lib.DG_TOPK_MAX_K}]")
+    _need_device([(row_table, "row_table"), (col_table, "col_table"), (G, "G"), (l, "l"), (row_idx, "row_idx"),
+                  (col_idx, "col_idx"), (rel_idx, "rel_idx")])
+    dev = G.device
+    vals = torch.empty((n, topk), dtype=torch.float32, device=dev)
+    idx = torch.empty((n, topk), dtype=torch.int32, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    chunks = top_relations_chunks(n, n_sel, max_workspace_bytes)
+    if chunks:
+        ws = torch.empty((chunks[0][1] - chunks[0][0], n_sel), dtype=torch.float32, device=dev)
+    for p0, p1 in chunks:
+        m = p1 - p0
+        _score_cross_call(row_table, col_table, row_idx, col_idx, G, l, rel_idx, dims, p0, m, ws, stream)
+        _row_topk_call(ws[:m], topk, vals[p0:p1], idx[p0:p1], counts[p0:p1], stream)
+    return vals, idx, counts
+
+
 def decoder_score_bf16(row_table: torch.Tensor, col_table: torch.Tensor, rows: torch.Tensor,
                        cols: torch.Tensor, G: torch.Tensor, l_table: Optional[torch.Tensor] = None,
                        rel: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,

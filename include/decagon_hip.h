@@ -1002,6 +1002,63 @@ int32_t dg_seg_tile_lookup(const int32_t* seg_ptr, int32_t n_seg, int32_t tile, 
                            int32_t* local);
 
 /* --------------------------------------------------------------------------------------
+ * The profile of node pairs: every relation of one edge type scored for given pairs, and the
+ * best relations of every pair (additive to ABI 39).
+ * Replaces NpPredictor(relationId)._predictEdges (main/Predictor/NpPredictor.py:293-313: the
+ * E·D·R·D·Eᵀ matrix of ONE relation, then the wanted entries) looped over relations, and the
+ * per-relation session.run(predictions) of DecagonAccuracyEvaluator._computePredictions.
+ *
+ * dg_decoder_score_cross_f32: for pair p < n_pairs and slot s < n_sel with k = rel_idx[s]
+ * (rel_idx device int32 [n_sel]; NULL: k = s),
+ *
+ *     out[p*ld_out + s] = (row_table[row_idx[p]] ∘ l_k)ᵀ · G_k · (l_k ∘ col_table[col_idx[p]])
+ *
+ * with the operand conventions of dg_decoder_topk_f32 and dg_decoder_score_seg_f32 (G_k = G +
+ * k*g_stride, g_stride 0 or d*d; l_k = l + k*l_stride, l_stride 0 or d; l NULL = identity) and d
+ * 32 or 64.  rel_idx may repeat relations, in any order.  ld_out >= n_sel; columns
+ * [n_sel, ld_out) of a row are not written.  Every out[p, s] equals, bit for bit, what
+ * dg_decoder_score_f32 returns for that pair with G_k, l_k, whatever the pair's place in the
+ * call.  A pair whose index lies outside [0, n_rows) x [0, n_cols) gets a whole row of NaN, a
+ * slot whose relation lies outside [0, n_rel) a whole column of NaN; nothing out of range is
+ * read.  Asynchronous on `stream`; allocates nothing and reads nothing on the host (graph
+ * capture).  n_pairs == 0 succeeds without a launch.
+ * Rejected on the host, before any HIP call: DG_EINVAL for a NULL table, G, or (n_pairs > 0)
+ * index or out; n_sel < 1, n_rel < 1, n_pairs < 0, empty tables; d not 32 or 64; ld_row or
+ * ld_col < d; ld_out < n_sel; a stride other than the two allowed; rel_idx NULL with a
+ * per-relation operand and n_sel > n_rel; n_pairs * ld_out >= DG_CROSS_MAX_OUT (2^38 elements:
+ * it keeps the grid of ⌈n_pairs/32⌉·⌈n_sel/C⌉ waves 32-bit; the offsets into out are 64-bit) or
+ * n_pairs > 2^31 − 65 (32-bit pair offsets).
+ * DG_EALIGN for row_table or col_table not 16-byte aligned or ld_row / ld_col not a multiple of
+ * 4 (the rules of dg_decoder_topk_f32; G and l need no alignment).
+ *
+ * dg_decoder_score_cross_chunk: the slot chunk C that call uses for (n_pairs, n_sel) — one wave
+ * scores one 32-pair tile against C consecutive slots; C is 32, halved down to 4 while the grid
+ * would leave SIMDs idle (0 for n_pairs < 0 or n_sel < 1).  Host only; for tests and tools.
+ *
+ * dg_row_topk_f32: for every row r < n_rows of x (row r at x + r*ld, ld >= n_cols) the `topk`
+ * highest entries among columns [0, n_cols), descending, in the total order of
+ * dg_decoder_topk_f32 with the column as the index: higher fp32 value first, equal values by
+ * smaller column, −0 compares and is returned as +0, non-finite values by bit pattern with no
+ * further promise.  out_val float / out_idx int32 [n_rows x topk], out_count int32 [n_rows] =
+ * min(topk, n_cols); slots past the count hold −inf / −1.  1 <= topk <= DG_TOPK_MAX_K,
+ * 1 <= n_cols < 2^31.  One wave per row keeps the list in LDS: no workspace is needed —
+ * dg_row_topk_workspace returns 0 and a NULL workspace is accepted.  Asynchronous; n_rows == 0
+ * succeeds without a launch.
+ * -------------------------------------------------------------------------------------- */
+#define DG_CROSS_MAX_OUT (1ll << 38)
+int dg_decoder_score_cross_f32(const float* row_table, int64_t ld_row, int32_t n_rows,
+                               const float* col_table, int64_t ld_col, int32_t n_cols,
+                               const int32_t* row_idx, const int32_t* col_idx, int32_t n_pairs,
+                               const float* G, int64_t g_stride, const float* l, int64_t l_stride,
+                               const int32_t* rel_idx, int32_t n_sel, int32_t n_rel, int32_t d,
+                               float* out, int64_t ld_out, void* stream);
+int32_t dg_decoder_score_cross_chunk(int32_t n_pairs, int32_t n_sel);
+int64_t dg_row_topk_workspace(int32_t n_rows, int32_t n_cols, int32_t topk);
+int dg_row_topk_f32(const float* x, int64_t ld, int32_t n_rows, int32_t n_cols, int32_t topk,
+                    float* out_val, int32_t* out_idx, int32_t* out_count, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------------------
  * Unigram negative sampler (T11):  out[i] ~ Categorical(p), p_c ∝ degree_c^0.75, draw
  * (offset + i) of a counter-based hash stream, through a Walker alias table of `range`
  * entries {acceptance probability as float bits, alias index} (uint32 pairs, built once on
