@@ -320,6 +320,17 @@ SIGNATURES = {
     "dg_row_topk_workspace": (c_int64, [c_int32, c_int32, c_int32]),
     "dg_row_topk_f32": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_int64, c_void_p]),
+    "dg_decoder_grad_seg_workspace": (c_int64, [c_int32, c_int32]),
+    "dg_decoder_grad_seg_f32": (
+        c_int32,
+        [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
+    ),
+    "dg_segment_rows_sum_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                                          c_int64, c_int32, c_void_p]),
+    "dg_segment_rows_sum_chunk": (c_int32, []),
+    "dg_segment_rows_sum_waves": (c_int32, []),
     "dg_unigram_sample_slots": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, ctypes.c_uint64,
                                           c_void_p, c_void_p]),
     "dg_unigram_sample": (

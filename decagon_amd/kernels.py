@@ -1570,15 +1570,20 @@ def unigram_sample(table: torch.Tensor, n: int, seed: int, offset: int,
 
 
 def unigram_sample_slots(table: torch.Tensor, slot0: int, batch: int, n: int, seed: int,
-                         out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+                         out: Optional[torch.Tensor] = None, stream=None, first_slot: int = 0) -> torch.Tensor:
     """n draws, draw i from the alias table of relation slot slot0 + i // batch (table: int32
     [n_slots, range, 2], one per GLOBAL slot; or a shared [range, 2]) — counter slot0·batch + i,
-    so the draws do not depend on how slots are dealt to ranks (dg_unigram_sample_slots)."""
+    so the draws do not depend on how slots are dealt to ranks (dg_unigram_sample_slots).
+    first_slot: the global slot of table[0] when the table holds only slots [first_slot,
+    first_slot + n_slots) (the entry point is given the address slot 0's table would have; it
+    reads the slots it draws from only)."""
     _dev(table, torch.int32, "alias table")
+    base = table.data_ptr()
     if table.dim() == 3 and table.shape[2] == 2 and table.is_contiguous():
         rng, stride = table.shape[1], table.shape[1]
-        if slot0 + -(-n // batch) > table.shape[0]:
+        if first_slot < 0 or slot0 < first_slot or slot0 - first_slot + -(-n // batch) > table.shape[0]:
             raise ValueError("slot range outside the alias tables")
+        base = (base - first_slot * stride * 8) % 2**64
     elif table.dim() == 2 and table.shape[1] == 2:
         rng, stride = table.shape[0], 0
     else:
@@ -1588,7 +1593,7 @@ def unigram_sample_slots(table: torch.Tensor, slot0: int, batch: int, n: int, se
     _dev(out, torch.int32, "out")
     if out.numel() < n:
         raise ValueError("out too small")
-    check(_lib.load().dg_unigram_sample_slots(table.data_ptr(), rng, stride, slot0, batch, n, seed & (2**64 - 1),
+    check(_lib.load().dg_unigram_sample_slots(base, rng, stride, slot0, batch, n, seed & (2**64 - 1),
                                                out.data_ptr(), _stream_ptr(stream)), "dg_unigram_sample_slots")
     return out
 
@@ -1841,6 +1846,137 @@ def scatter_rows(idx: torch.Tensor, src: torch.Tensor, out: torch.Tensor, stream
         raise ValueError("scatter_rows: shapes")
     check(_lib.load().dg_scatter_rows_f32(idx.data_ptr(), n, src.data_ptr(), src.shape[1], out.data_ptr(),
                                           out.stride(0), out.shape[0], _stream_ptr(stream)), "dg_scatter_rows_f32")
+
+
+class PreparedDecoderGradSeg:
+    """dg_decoder_grad_seg_f32 for the packed batches of one edge type: per pair p of segment s
+    (relation k = seg_rel[s]; None: k = s), `mv[p]` = a_p·M_k·v_p (the gradient of the negative
+    row; minus it that of the positive row) and `grad_cols[p]`, and the decoder variables'
+    gradients (each written only if its tensor is given): dG [d, d] (G shared: summed over the
+    segments) or [K, d, d], dG_diag [K, d], dl [K, d].  The relations of the segments must be
+    distinct; outputs of relations without a segment are left untouched.
+
+    G: [d, d] or [K, d, d]; l: None, [d] or [K, d]; seg_ptr device int32 [n_seg + 1], never read
+    on the host."""
+
+    def __init__(self, row_table, col_table, rows, cols, neg_rows, seg_ptr, seg_rel, pos, neg, G, l,
+                 margin: float, dG: Optional[torch.Tensor] = None, dl: Optional[torch.Tensor] = None,
+                 dG_diag: Optional[torch.Tensor] = None):
+        for t, nm, dt in ((row_table, "row_table", torch.float32), (col_table, "col_table", torch.float32),
+                          (rows, "rows", torch.int32), (cols, "cols", torch.int32),
+                          (neg_rows, "neg_rows", torch.int32), (seg_ptr, "seg_ptr", torch.int32),
+                          (pos, "pos", torch.float32), (neg, "neg", torch.float32), (G, "G", torch.float32)):
+            _dev(t, dt, nm)
+        if seg_rel is not None:
+            _dev(seg_rel, torch.int32, "seg_rel")
+        if l is not None:
+            _dev(l, torch.float32, "l")
+        if row_table.dim() != 2 or col_table.dim() != 2 or G.dim() not in (2, 3):
+            raise ValueError("decoder_grad_seg: tables must be [N, d] and G [d, d] or [K, d, d]")
+        d = G.shape[-1]
+        if d not in (32, 64):
+            raise ValueError(f"decoder_grad_seg: d = {d} unsupported (32 or 64)")
+        if G.shape[-2] != d or row_table.shape[1] != d or col_table.shape[1] != d:
+            raise ValueError("decoder_grad_seg: d mismatch")
+        if l is not None and (l.dim() not in (1, 2) or l.shape[-1] != d):
+            raise ValueError("decoder_grad_seg: d mismatch (l must be [d] or [K, d])")
+        if row_table.shape[0] < 1 or col_table.shape[0] < 1:
+            raise ValueError("decoder_grad_seg: empty table")
+        n = rows.numel()
+        if any(t.numel() != n for t in (cols, neg_rows, pos, neg)):
+            raise ValueError("decoder_grad_seg: batch sizes differ")
+        n_seg = seg_ptr.numel() - 1
+        if n_seg < 1:
+            raise ValueError("decoder_grad_seg: seg_ptr must have n_seg + 1 >= 2 entries")
+        if seg_rel is not None and seg_rel.numel() != n_seg:
+            raise ValueError("decoder_grad_seg: seg_rel must have one entry per segment")
+        g_per, l_per = G.dim() == 3, l is not None and l.dim() == 2
+        ks = {int(t.shape[0]) for t, per in ((G, g_per), (l, l_per)) if per}
+        if len(ks) > 1:
+            raise ValueError(f"decoder_grad_seg: relation counts disagree: {sorted(ks)}")
+        K = ks.pop() if ks else None
+        if K is not None and seg_rel is None and n_seg > K:
+            raise ValueError(f"decoder_grad_seg: {n_seg} segments but {K} relations (pass seg_rel)")
+        if dl is not None and not l_per:
+            raise ValueError("dl needs a per-relation diagonal l [K, d]")
+        if dG_diag is not None and not g_per:
+            raise ValueError("dG_diag needs a per-relation G [K, d, d]")
+        n_out = K if K is not None else n_seg
+        for t, nm, sz in ((dG, "dG", (n_out if g_per else 1) * d * d), (dl, "dl", n_out * d),
+                          (dG_diag, "dG_diag", n_out * d)):
+            if t is not None:
+                _dev(t, torch.float32, nm)
+                if t.numel() != sz:
+                    raise ValueError(f"{nm} must have {sz} elements")
+        dev = G.device
+        self.mv = torch.empty((n, d), device=dev)
+        self.grad_cols = torch.empty((n, d), device=dev)
+        lib = _lib.load()
+        nbytes = int(lib.dg_decoder_grad_seg_workspace(n_seg, d))
+        vars_ = dG is not None or dl is not None or dG_diag is not None
+        self._ws = torch.empty(max(1, nbytes // 4), device=dev) if vars_ else None
+        self._keep = (row_table, col_table, rows, cols, neg_rows, seg_ptr, seg_rel, pos, neg, G, l, dG, dl, dG_diag)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        n_rel = K if K is not None else (2**31 - 1 if seg_rel is not None else n_seg)
+        self._args = [row_table.data_ptr(), d, row_table.shape[0], col_table.data_ptr(), d, col_table.shape[0],
+                      ptr(rows) if n else None, ptr(cols) if n else None, ptr(neg_rows) if n else None,
+                      seg_ptr.data_ptr(), ptr(seg_rel), n_seg, n, ptr(pos) if n else None, ptr(neg) if n else None,
+                      float(margin), G.data_ptr(), d * d if g_per else 0, ptr(l), d if l_per else 0, n_rel, d,
+                      ptr(self.mv) if n else None, ptr(self.grad_cols) if n else None, ptr(dG), ptr(dl),
+                      ptr(dG_diag), ptr(self._ws), nbytes if vars_ else 0]
+        self._fn = lib.dg_decoder_grad_seg_f32
+
+    def __call__(self, stream=None) -> None:
+        check(self._fn(*self._args, _stream_ptr(stream)), "dg_decoder_grad_seg_f32")
+
+
+def segment_rows_chunk() -> Tuple[int, int]:
+    """(items per wave chunk, waves per output row) of segment_rows_sum's launch."""
+    lib = _lib.load()
+    return int(lib.dg_segment_rows_sum_chunk()), int(lib.dg_segment_rows_sum_waves())
+
+
+def occurrence_list(idx: torch.Tensor, n_out_rows: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The node-major occurrence list of an index array (device plumbing: one stable sort):
+    (node_ptr int32 [n_out_rows + 1], order int32 [n]) with order[node_ptr[r] : node_ptr[r+1]] the
+    positions q of idx[q] == r, ascending.  Indices outside [0, n_out_rows) are in no list."""
+    # (keys in the narrowest type that holds [-1, n_out_rows]: the radix sort's passes follow its width)
+    kt = torch.int16 if n_out_rows < 2**15 - 1 else torch.int32
+    key, order = torch.sort(idx.clamp(-1, n_out_rows).to(kt), stable=True)
+    bounds = torch.arange(n_out_rows + 1, device=idx.device, dtype=kt)
+    node_ptr = torch.searchsorted(key, bounds).to(torch.int32)
+    return node_ptr, order.to(torch.int32)
+
+
+def segment_rows_sum(node_ptr: torch.Tensor, item: torch.Tensor, src: torch.Tensor, out: torch.Tensor,
+                     sign: Optional[torch.Tensor] = None, stream=None) -> None:
+    """out[r] += Σ_q sign[q]·src[item[q]] for q in [node_ptr[r], node_ptr[r+1]) in q order
+    (dg_segment_rows_sum_f32; fixed order: bitwise reproducible).  Items outside src's rows add
+    nothing."""
+    _dev(node_ptr, torch.int32, "node_ptr")
+    _dev(item, torch.int32, "item")
+    _dev(src, torch.float32, "src")
+    # (out may be a column block of a wider buffer: rows ld_out = out.stride(0) apart)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32:
+        raise TypeError("out: expected a float32 device tensor")
+    if sign is not None:
+        _dev(sign, torch.float32, "sign")
+        if sign.numel() != item.numel():
+            raise ValueError("segment_rows_sum: one sign per item")
+    if src.dim() != 2 or out.dim() != 2 or out.shape[1] != src.shape[1]:
+        raise ValueError("segment_rows_sum: shapes")
+    if out.shape[0] > 1 and (out.stride(1) != 1 or out.stride(0) < out.shape[1]):
+        raise ValueError("segment_rows_sum: out's rows must be dense and at least d apart")
+    if not 1 <= src.shape[1] <= 256:
+        raise ValueError("segment_rows_sum: d must be in [1, 256]")
+    if node_ptr.numel() != out.shape[0] + 1:
+        raise ValueError("segment_rows_sum: node_ptr must have one entry per output row, plus one")
+    check(_lib.load().dg_segment_rows_sum_f32(node_ptr.data_ptr(), item.data_ptr(),
+                                              sign.data_ptr() if sign is not None else None, item.numel(),
+                                              src.data_ptr(), src.shape[0], src.shape[1], out.data_ptr(),
+                                              max(out.stride(0), out.shape[1]), out.shape[0],
+                                              _stream_ptr(stream)),
+          "dg_segment_rows_sum_f32")
 
 
 class PreparedL2Grad:

@@ -215,9 +215,9 @@ class DecagonOptimizer:
                 ref[0].add_bytes(ref[1], torch.cuda.memory_allocated(ctx.session.device) - before)
         return fwd, plans[id(self)]
 
-    def _decoder_grads(self, ctx: RunContext, model, e: int, rt: int, ct: int):
-        """Zeroed gradient buffers of every decoder, the batch relation's entries filled
-        (TF's gather over the stacked latent lists gives the others dense zeros)."""
+    def _decoder_grad_buffers(self, ctx: RunContext, model):
+        """The session's gradient buffer of every decoder (one flat tensor per edge type, laid
+        out as the decoder's parameters), zeroed."""
         key = ("dec_grads", id(self))
         cache = ctx.session.caches
         if key not in cache:
@@ -225,14 +225,21 @@ class DecagonOptimizer:
         grads = cache[key]
         for t in grads.values():
             t.zero_()
+        return grads
+
+    @staticmethod
+    def _grad_view(dec, gflat: torch.Tensor, var) -> torch.Tensor:
+        """The slice of a decoder's flat gradient buffer that belongs to `var`."""
+        off = (var.tensor.data_ptr() - dec.flat.data_ptr()) // 4
+        return gflat[off:off + var.tensor.numel()]
+
+    def _decoder_grads(self, ctx: RunContext, model, e: int, rt: int, ct: int):
+        """Zeroed gradient buffers of every decoder, the batch relation's entries filled
+        (TF's gather over the stacked latent lists gives the others dense zeros)."""
+        grads = self._decoder_grad_buffers(ctx, model)
         i, j, k = self._rel_of[e]
         dec = model.edge_type2decoder[i, j]
-        gflat = grads[i, j]
-
-        def gview(var):
-            off = (var.tensor.data_ptr() - dec.flat.data_ptr()) // 4
-            return gflat[off:off + var.tensor.numel()]
-
+        gview = lambda var: self._grad_view(dec, grads[i, j], var)  # noqa: E731
         gk, gv, lk, lv = model._latent_spec[e]
         fed = ctx.is_fed(self.latent_inters[e]) or ctx.is_fed(self.latent_varies[e])
         out = {"dG": None, "dl": None, "dG_diag": None}
@@ -273,6 +280,11 @@ class DecagonOptimizer:
             kernels.scatter_rows(cols, op.grad_cols, dE[ct])
 
         tp.backward(decoder_grad)
+        return self._finish_step(ctx, model, tp, dec_grads, apply)
+
+    def _finish_step(self, ctx: RunContext, model, tp, dec_grads, apply: bool):
+        """After tp.backward: the (gradient, variable) list (apply=False), or one Adam step on
+        every variable with the session's slots of this optimizer."""
         w1, w2 = model.weight_stacks()
         ets = list(model.edge_types)
         pairs = tp.adam_pairs(w1, w2)  # whole stacks (one GPU) or the local relations (sharded)

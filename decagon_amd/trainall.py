@@ -1,0 +1,257 @@
+"""One training step on a batch of EVERY relation: the summed hinge cost Σ_(i,j) Σ_k cost_ijk.
+
+The reference trains one (relation, batch) at a time (decagon/deep/optimizer.py:108-114 driven by
+decagon/deep/minibatch.py:278-313): every step pays the whole two-layer forward, the whole
+backward through both GCN layers over every relation and Adam on every variable, for the 512
+edges of one side effect.  Neither GCN pass depends on the relation the batch came from — only
+the decoder's gradient and its scatter into dE do — and the gradient of a sum of costs is the
+sum of the gradients.  `train_step_all` therefore takes a batch of every relation, fills ONE dE
+and runs one GCN backward and one Adam update: gradient accumulation over relations.
+
+Per edge type: one sampler call (dg_unigram_sample_slots, unless the negatives are fed), one
+scorer launch over the positive and negative pairs (dg_decoder_score_seg_f32), one hinge sum
+(dg_hinge_loss_ws_f32), one segmented decoder gradient (dg_decoder_grad_seg_f32) and two
+row reductions into dE (dg_segment_rows_sum_f32 over node-major occurrence lists, built by
+one stable device sort each).  The forward, the TrainPlan, the dropout masks, the embeddings
+tables and the Adam slots are those of `opt_op`, so all-relation steps and ordinary steps mix.
+"""
+from __future__ import annotations
+
+from typing import Dict, Mapping, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import kernels
+from .evaluate import _stacked_latents
+from .graph import InvalidArgumentError, Node, RunContext
+
+EdgeType = Tuple[int, int]
+
+
+def _items(per_rel):
+    """(relation, array) pairs of a mapping, or of a sequence of such pairs."""
+    return list(per_rel.items()) if isinstance(per_rel, Mapping) else [(k, v) for k, v in per_rel]
+
+
+def pack_batches(batches, edge_types, shapes) -> Dict[EdgeType, Dict[str, np.ndarray]]:
+    """Pack {edge type (i, j): {relation k: int array [n_k, 2] of (row, col)}} for the segmented
+    kernels (host): per edge type int32 `rows`, `cols` [Σ n_k], `seg_ptr` [n_seg + 1] and
+    `seg_rel` [n_seg], one segment per listed relation in the order given.  Empty batches are
+    allowed (an empty segment).  A relation's batches may also be given as a sequence of
+    (k, array) pairs.
+
+    edge_types: {(i, j): number of relations}; shapes: {(i, j): (rows of type i, rows of type j)}.
+    ValueError: an unknown edge type or relation, a relation listed twice, an index outside the
+    edge type's shape, an array that is not [n, 2]."""
+    out = {}
+    for et, per_rel in _items(batches):
+        et = tuple(int(x) for x in et) if isinstance(et, (tuple, list)) else et
+        if et not in edge_types:
+            raise ValueError(f"unknown edge type {et}")
+        K = int(edge_types[et])
+        n_r, n_c = (int(x) for x in shapes[et])
+        arrs, rels, seen = [], [], set()
+        for k, b in _items(per_rel):
+            if int(k) != k or not 0 <= int(k) < K:
+                raise ValueError(f"edge type {et}: unknown relation {k!r} (it has {K})")
+            k = int(k)
+            if k in seen:
+                raise ValueError(f"edge type {et}: relation {k} listed twice")
+            seen.add(k)
+            b = np.asarray(b)
+            if b.size == 0:
+                b = np.zeros((0, 2), np.int64)
+            if b.ndim != 2 or b.shape[1] != 2 or b.dtype.kind not in "iu":
+                raise ValueError(f"edge type {et}, relation {k}: a batch is an integer array [n, 2]")
+            arrs.append(b)
+            rels.append(k)
+        ptr = np.zeros(len(arrs) + 1, np.int64)
+        np.cumsum([b.shape[0] for b in arrs], out=ptr[1:])
+        cat = np.concatenate(arrs).astype(np.int64, copy=False) if arrs else np.zeros((0, 2), np.int64)
+        # (the indices of all relations are checked at once; the culprit is looked up only on failure)
+        bad = (cat < 0) | (cat >= np.asarray([n_r, n_c]))
+        if bad.any():
+            k = rels[int(np.searchsorted(ptr, int(np.nonzero(bad.any(axis=1))[0][0]), side="right")) - 1]
+            raise ValueError(f"edge type {et}, relation {k}: index outside {(n_r, n_c)}")
+        if ptr[-1] >= 2**31:
+            raise ValueError(f"edge type {et}: too many pairs")
+        out[et] = {"rows": np.ascontiguousarray(cat[:, 0], np.int32), "cols": np.ascontiguousarray(cat[:, 1], np.int32),
+                   "seg_ptr": ptr.astype(np.int32), "seg_rel": np.asarray(rels, np.int32)}
+    return out
+
+
+def occurrence_list(idx: np.ndarray, n_out_rows: int):
+    """The node-major occurrence list of an index array, on the host (what
+    kernels.occurrence_list builds on the device): (node_ptr [n_out_rows + 1], order) with
+    order[node_ptr[r] : node_ptr[r+1]] the positions of r in idx, ascending; indices outside
+    [0, n_out_rows) are in no list."""
+    idx = np.asarray(idx, np.int64)
+    order = np.argsort(idx, kind="stable")
+    node_ptr = np.searchsorted(idx[order], np.arange(n_out_rows + 1))
+    return node_ptr.astype(np.int32), order.astype(np.int32)
+
+
+def row_occurrences(rows: np.ndarray, neg_rows: np.ndarray, n_out_rows: int):
+    """The row side's list for dg_segment_rows_sum_f32 over `mv` (stored once per pair): the
+    occurrences of a node among the positive rows (sign −1) and the negative rows (sign +1),
+    positives first: (node_ptr, item = the pair, sign)."""
+    n = len(rows)
+    node_ptr, order = occurrence_list(np.concatenate([rows, neg_rows]), n_out_rows)
+    return node_ptr, (order % max(n, 1)).astype(np.int32), np.where(order < n, -1.0, 1.0).astype(np.float32)
+
+
+def _negatives(neg_samples, packed, shapes) -> Dict[EdgeType, np.ndarray]:
+    """Fed negatives, packed in the batches' segment order (one negative row per pair)."""
+    out = {}
+    for et, p in packed.items():
+        if et not in neg_samples:
+            raise ValueError(f"neg_samples has no entry for edge type {et}")
+        per = dict(_items(neg_samples[et]))
+        segs = []
+        for s, k in enumerate(p["seg_rel"]):
+            n = int(p["seg_ptr"][s + 1] - p["seg_ptr"][s])
+            a = np.asarray(per.get(int(k), np.zeros(0, np.int64))).reshape(-1)
+            if a.size != n:
+                raise ValueError(f"edge type {et}, relation {int(k)}: {a.size} negatives for {n} pairs")
+            if n and (a.min() < 0 or a.max() >= shapes[et][0]):
+                raise ValueError(f"edge type {et}, relation {int(k)}: negative row outside [0, {shapes[et][0]})")
+            segs.append(a)
+        out[et] = (np.concatenate(segs) if segs else np.zeros(0)).astype(np.int32)
+    return out
+
+
+def _alias_stack(ctx: RunContext, opt, et: EdgeType, first: int, K: int) -> torch.Tensor:
+    """The alias tables of an edge type's K relations as one [K, range, 2] tensor (session cache)."""
+    key = ("sampler_stack", id(opt), et)
+    cache = ctx.session.caches
+    if key not in cache:
+        cache[key] = torch.stack(opt._sampler(ctx).tables[first:first + K]).contiguous()
+    return cache[key]
+
+
+def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None, apply: bool = True):
+    """One step on Σ_(i,j) Σ_k hinge cost of relation k's batch (module docstring).
+
+    batches: {(i, j): {k: int array [n_k, 2]}} (pack_batches' input).  neg_samples, in the same
+    nesting ({(i, j): {k: int array [n_k]}}), feeds the negative rows; None draws relation k's
+    from its own degree table on the device (dg_unigram_sample_slots with the optimizer's seed:
+    the relations' tables gathered in segment order, draw c of the call's stream numbered
+    slot0·n + c with n the common batch size and slot0 = ⌈draw counter / n⌉; the counter then
+    stands after the last draw, so it advances by the number of draws whenever it was a multiple
+    of n).  Drawing needs equal n_k within an edge type; otherwise feed the negatives.
+
+    apply=True: one Adam update of every variable, with the slots `opt_op` uses (Adam's t advances
+    once); returns the cost (float, before the update).  apply=False: (cost, grads_vars) with
+    grads_vars exactly as `opt.grads_vars` returns it, nothing updated.
+
+    NotImplementedError for a sharded session; InvalidArgumentError when a decoder latent of a
+    trained edge type, or `outputs` / `neg_outputs` / `cost`, is fed."""
+    model = opt._model()
+    if getattr(sess, "shard", None) is not None:
+        raise NotImplementedError("train_step_all runs on one GPU (the session is sharded)")
+    shapes = {et: tuple(int(x) for x in opt.edge_type2dim[et][0]) for et in model.edge_types}
+    packed = pack_batches(batches, model.edge_types, shapes)
+    if neg_samples is None:
+        for et, p in packed.items():
+            if len(set(np.diff(p["seg_ptr"]).tolist())) > 1:
+                raise ValueError(f"edge type {et}: batch sizes differ between relations; feed neg_samples")
+        negs_host = None
+    else:
+        negs_host = _negatives(neg_samples, packed, shapes)
+    ets = list(model.edge_types)
+
+    def fn(ctx: RunContext):
+        if not ctx.training:
+            raise RuntimeError("training ops must be fetched through Session.run")
+        for nd in (opt.outputs, opt.neg_outputs, opt.cost):
+            if ctx.is_fed(nd):
+                raise InvalidArgumentError(f"{nd.name} is fed: the cost's gradient does not reach the model")
+        for et in packed:
+            first = sum(model.edge_types[t] for t in ets[:ets.index(et)])
+            for r in range(first, first + model.edge_types[et]):
+                if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
+                    raise InvalidArgumentError("train_step_all trains the decoder's variables; a latent matrix is fed")
+        fwd, tp = opt._train_plan(ctx, model)
+        if tp.sharded:
+            raise NotImplementedError("train_step_all runs on one GPU (the plan is sharded)")
+        dev = ctx.session.device
+        dec_grads = opt._decoder_grad_buffers(ctx, model)
+        costs, work = [], []
+        for et, p in packed.items():
+            i, j = et
+            n, n_seg = int(p["seg_ptr"][-1]), len(p["seg_rel"])
+            if n == 0:
+                continue
+            K = model.edge_types[et]
+            dec = model.edge_type2decoder[et]
+            row_t, col_t = opt._tables(ctx, i, j)
+            d = row_t.shape[1]
+            G, l = _stacked_latents(ctx, dec, d)
+            fed = negs_host is not None
+            # one upload: [rows | cols | (negatives) | seg_ptr | seg_ptr + n | seg_rel | seg_rel]
+            host = np.concatenate([p["rows"], p["cols"]] + ([negs_host[et]] if fed else []) +
+                                  [p["seg_ptr"], p["seg_ptr"][1:] + n, p["seg_rel"], p["seg_rel"]]).astype(np.int32)
+            buf = torch.from_numpy(host).to(dev)
+            rows, cols = buf[:n], buf[n:2 * n]
+            o = 3 * n if fed else 2 * n
+            seg2, o = buf[o:o + 2 * n_seg + 1], o + 2 * n_seg + 1
+            rel2 = buf[o:o + 2 * n_seg]
+            seg_ptr, seg_rel = seg2[:n_seg + 1], rel2[:n_seg]
+            if fed:
+                negs = buf[2 * n:3 * n]
+            else:
+                first = sum(model.edge_types[t] for t in ets[:ets.index(et)])
+                s = opt._sampler(ctx)
+                stack = _alias_stack(ctx, opt, et, first, K)
+                if stack.shape[1] > row_t.shape[0]:
+                    raise InvalidArgumentError("degrees list longer than the row embedding table")
+                nk = n // n_seg  # (equal batch sizes, and n > 0: every segment holds nk >= 1 pairs)
+                slot0 = -(-s.counter // nk)
+                tabs = stack.index_select(0, seg_rel.long()).contiguous()
+                negs = kernels.unigram_sample_slots(tabs, slot0, nk, n, opt.seed, first_slot=slot0)
+                s.counter = (slot0 + n_seg) * nk
+            # positives, then negatives (the positive batch's columns: optimizer.py:51-57)
+            scores = kernels.decoder_score_seg(row_t, col_t, torch.cat([rows, negs]), torch.cat([cols, cols]), seg2,
+                                               G, l, seg_rel=rel2)
+            pos, neg = scores[:n], scores[n:]
+            costs.append(kernels.hinge_loss(pos, neg, opt.margin, workspace=kernels.hinge_workspace(dev)))
+            gflat = dec_grads[et]
+            outs = {"dG": None, "dl": None, "dG_diag": None}
+            specs = [dec.latent(k) for k in range(K)]
+            gk, lk = specs[0][0], specs[0][2]
+
+            def stacked(c, per):  # the K variables' gradient slices as one [K, per] view of gflat
+                off0 = (specs[0][c].tensor.data_ptr() - dec.flat.data_ptr()) // 4
+                return gflat[off0:off0 + K * per]
+
+            if gk == "dense":
+                shared = all(sp[1] is specs[0][1] for sp in specs)
+                outs["dG"] = opt._grad_view(dec, gflat, specs[0][1]) if shared else stacked(1, d * d)
+            elif gk == "diag":
+                outs["dG_diag"] = stacked(1, d)
+            if lk == "diag":
+                outs["dl"] = stacked(3, d)
+            op = kernels.PreparedDecoderGradSeg(row_t, col_t, rows, cols, negs, seg_ptr, seg_rel, pos, neg, G, l,
+                                                opt.margin, **outs)
+            work.append((i, j, n, rows, cols, negs, op))
+
+        def decoder_grad(dE):
+            for i, j, n, rows, cols, negs, op in work:
+                op()
+                node_ptr, order = kernels.occurrence_list(torch.cat([rows, negs]), dE[i].shape[0])
+                sign = torch.where(order < n, -1.0, 1.0).to(torch.float32)
+                kernels.segment_rows_sum(node_ptr, torch.remainder(order, n).to(torch.int32), op.mv, dE[i], sign=sign)
+                node_ptr, order = kernels.occurrence_list(cols, dE[j].shape[0])
+                kernels.segment_rows_sum(node_ptr, order, op.grad_cols, dE[j])
+
+        tp.backward(decoder_grad)
+        # (the edge types' sums are added on the host, in float64)
+        cost = torch.cat([c.reshape(1) for c in costs]) if costs else torch.zeros(1, device=dev)
+        return cost, opt._finish_step(ctx, model, tp, dec_grads, apply)
+
+    node = Node("trainall/step", fn)
+    node.training = True
+    cost, gv = sess.run(node, feed_dict=dict(feed_dict))
+    cost = float(np.asarray(cost, np.float64).sum())
+    return cost if apply else (cost, gv)

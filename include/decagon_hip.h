@@ -39,7 +39,10 @@ extern "C" {
 /* ABI version (39); bumped whenever a struct layout or a signature changes or an entry point is added
  * (36: DG_PEER_STATE_WORDS grew; 39: dg_decoder_topk_f32).  Added since 39 without a bump, purely
  * additive: dg_decoder_score_seg_f32, dg_rank_metrics_seg_workspace, dg_rank_metrics_seg_f32 and
- * the host helper dg_seg_tile_lookup (evaluation of all relations of an edge type in one pass). */
+ * the host helper dg_seg_tile_lookup (evaluation of all relations of an edge type in one pass);
+ * dg_decoder_grad_seg_workspace, dg_decoder_grad_seg_f32, dg_segment_rows_sum_f32 and the host
+ * helpers dg_segment_rows_sum_chunk / dg_segment_rows_sum_waves (the decoder backward of every
+ * relation's batch of an edge type in one pass). */
 int32_t dg_abi_version(void);
 
 /* --------------------------------------------------------------------------------------
@@ -1057,6 +1060,81 @@ int64_t dg_row_topk_workspace(int32_t n_rows, int32_t n_cols, int32_t topk);
 int dg_row_topk_f32(const float* x, int64_t ld, int32_t n_rows, int32_t n_cols, int32_t topk,
                     float* out_val, int32_t* out_idx, int32_t* out_count, void* workspace,
                     int64_t workspace_bytes, void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * The decoder backward of the hinge cost for every relation's batch of one edge type in one pass
+ * (additive to ABI 39).
+ * Replaces one tf.train.AdamOptimizer.minimize step per (relation, batch) (optimizer.py:108-114,
+ * minibatch.py:278-313) where only the decoder's gradient depends on the relation: the gradient
+ * of the summed cost Σ_k cost_k is the sum of the gradients, so one GCN backward and one Adam
+ * update serve a batch of every relation.
+ *
+ * dg_decoder_grad_seg_f32: dg_decoder_grad_f32 over packed SEGMENTS with the conventions of
+ * dg_decoder_score_seg_f32: segment s is pairs [seg_ptr[s], seg_ptr[s+1]) (seg_ptr int32
+ * [n_seg + 1] on the device, never read on the host; segments may be empty) and belongs to
+ * relation k = seg_rel[s] (seg_rel NULL: k = s), G_k = G + k*g_stride (g_stride 0 or d*d),
+ * l_k = l + k*l_stride (l_stride 0 or d; l NULL = identity), 0 <= k < n_rel.  The relations in
+ * seg_rel must be DISTINCT (two segments of one relation would both write its outputs).
+ * d is 32 or 64 (the per-segment dM buffer is n_seg*d*d floats).  With M_k = L_k·G_k·L_k, u / un
+ * / v the rows row_table[rows[p]] / row_table[neg_rows[p]] / col_table[cols[p]], and
+ * a_p = [neg[p] − (pos[p] − margin) > 0]:
+ *
+ *     mv[p]        = a_p · M_k·v_p                  float [n_pairs x d]
+ *     grad_cols[p] = a_p · M_kᵀ·(un_p − u_p)        float [n_pairs x d]
+ *     dM_s         = Σ_{p in s} a_p·(un_p − u_p)·v_pᵀ, pairs in order (workspace)
+ *
+ * mv is stored ONCE per pair: the gradient of the positive row u_p is −mv[p] and that of the
+ * negative row un_p is +mv[p]; the row reduction (dg_segment_rows_sum_f32) applies the signs.
+ * A pair with an index outside [0, n_rows) x [0, n_cols), and every pair of a segment whose
+ * relation lies outside [0, n_rel), gets zero rows and contributes nothing to dM (nothing out of
+ * range is read).  Rows of pairs outside every segment are not written.
+ * From dM a second, small launch writes the variables' gradients, each optional (NULL skips it):
+ *     dG       g_stride == 0: float [d x d] = Σ_s L_k·dM_s·L_k (DEDICOM's R), in a fixed order: the
+ *              segment list in 16 contiguous slices, each added in segment order, then the slices'
+ *              sums in slice order (one more launch);
+ *              g_stride != 0: dG[k] = L_k·dM_s·L_k, float [n_rel x d x d] (Bilinear)
+ *     dG_diag  dG_diag[k][a] = (L_k·dM_s·L_k)[a][a], float [n_rel x d]; needs g_stride != 0 (DistMult)
+ *     dl       dl[k][a] = Σ_b dM_s[a][b]·G_k[a][b]·l_k[b] + Σ_c dM_s[c][a]·G_k[c][a]·l_k[c],
+ *              float [n_rel x d]; needs l with l_stride == d (DEDICOM's D_k)
+ * Per-relation outputs of relations absent from seg_rel are left untouched (the caller zeroes
+ * the buffers); an empty segment's relation gets zeros.  Workspace: 16-byte aligned,
+ * dg_decoder_grad_seg_workspace(n_seg, d) bytes (0 for bad arguments), needed only when a
+ * variable output is requested.  Asynchronous; n_pairs == 0 succeeds without a launch.
+ * Rejected on the host before any HIP call: DG_EINVAL for d not 32 or 64, n_seg < 1, n_pairs < 0,
+ * a NULL table, seg_ptr or G, (n_pairs > 0) a NULL index, score or gradient array, empty tables,
+ * ld_row / ld_col < d, a stride other than the two allowed, seg_rel NULL with a per-relation
+ * operand and n_seg > n_rel, dl without a per-relation l, dG_diag with g_stride == 0, a missing or
+ * short workspace, n_pairs + 32*n_seg >= 2^31; DG_EALIGN for row_table, col_table, G, l or the
+ * workspace not 16-byte aligned, or ld_row / ld_col not a multiple of 4.
+ *
+ * dg_segment_rows_sum_f32: for every output row r < n_out_rows (row r at out + r*ld_out,
+ * ld_out >= d, 1 <= d <= 256)
+ *
+ *     out[r][:] += Σ_q sign[q] · src[item[q]][:],  q in [node_ptr[r], node_ptr[r+1]) in q order
+ *
+ * over a node-major occurrence list the caller builds once per batch (a stable sort of the index
+ * array): node_ptr int32 [n_out_rows + 1] ascending within [0, n_items], item int32 [n_items]
+ * rows of src (float [n_src_rows x d]), sign float [n_items] or NULL (all +1).  Items outside
+ * [0, n_src_rows) add nothing.  One workgroup of dg_segment_rows_sum_waves() waves owns a row:
+ * the list is cut into chunks of dg_segment_rows_sum_chunk() items, wave w adds chunks w,
+ * w + waves, ... in order, and the waves' sums are combined in a fixed tree — the result does not
+ * depend on scheduling, and a row with thousands of occurrences does not serialise on one wave.
+ * It replaces dg_scatter_rows_f32 (which scans the whole index array per pair) where n is large.
+ * The two helpers are host only, for tests and tools.
+ * -------------------------------------------------------------------------------------- */
+int64_t dg_decoder_grad_seg_workspace(int32_t n_seg, int32_t d);
+int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, int32_t n_rows, const float* col_table,
+                            int64_t ld_col, int32_t n_cols, const int32_t* rows, const int32_t* cols,
+                            const int32_t* neg_rows, const int32_t* seg_ptr, const int32_t* seg_rel,
+                            int32_t n_seg, int32_t n_pairs, const float* pos, const float* neg, float margin,
+                            const float* G, int64_t g_stride, const float* l, int64_t l_stride, int32_t n_rel,
+                            int32_t d, float* mv, float* grad_cols, float* dG, float* dl, float* dG_diag,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+int dg_segment_rows_sum_f32(const int32_t* node_ptr, const int32_t* item, const float* sign, int32_t n_items,
+                            const float* src, int32_t n_src_rows, int32_t d, float* out, int64_t ld_out,
+                            int32_t n_out_rows, void* stream);
+int32_t dg_segment_rows_sum_chunk(void);
+int32_t dg_segment_rows_sum_waves(void);
 
 /* --------------------------------------------------------------------------------------
  * Unigram negative sampler (T11):  out[i] ~ Categorical(p), p_c ∝ degree_c^0.75, draw
