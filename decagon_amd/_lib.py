@@ -337,6 +337,11 @@ SIGNATURES = {
         c_int32,
         [c_void_p, c_int32, c_int32, c_uint64, c_uint64, c_void_p, c_void_p],
     ),
+    "dg_epoch_batch_i32": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                     c_int32, ctypes.c_uint32, c_uint64, c_int32, c_int32, c_void_p, c_void_p,
+                                     c_void_p]),
+    "dg_epoch_perm_host": (c_int32, [c_int32, ctypes.c_uint32, c_void_p, c_void_p, c_int64]),
+    "dg_epoch_key_host": (ctypes.c_uint32, [c_uint64, ctypes.c_uint32, ctypes.c_uint32]),
 }
 
 _LIB = None

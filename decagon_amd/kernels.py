@@ -1598,6 +1598,66 @@ def unigram_sample_slots(table: torch.Tensor, slot0: int, batch: int, n: int, se
     return out
 
 
+def epoch_batch(edges: torch.Tensor, edge_ptr: torch.Tensor, seg_rel: torch.Tensor,
+                wrap_mask: Optional[torch.Tensor], batch: int, t: int, epoch: int, seed: int, first_slot: int,
+                bad_row: int, rows: Optional[torch.Tensor] = None, cols: Optional[torch.Tensor] = None,
+                stream=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Step t's batch of `batch` pairs for every listed relation of one edge type, gathered from
+    its device-resident edges in the epoch's shuffled order (dg_epoch_batch_i32): (rows, cols),
+    int32 [n_seg·batch] in the segmented kernels' layout, segment s of relation seg_rel[s].
+
+    edges: int32 [n_edges, 2] (row, col), relation-major; edge_ptr: int64 [K + 1]; seg_rel: int32
+    [n_seg]; wrap_mask: None or int32 [⌈K/32⌉], bit k set when relation k wraps round (batch
+    t mod ⌊n_k/batch⌋) instead of leaving the epoch at t >= ⌊n_k/batch⌋.  Relation k's order is
+    epochs.perm under epochs.epoch_key(seed, epoch, first_slot + k).  A segment without a batch
+    gets rows `bad_row` (the row table's length) and columns 0.  Asynchronous."""
+    for tns, nm, dt in ((edges, "edges", torch.int32), (edge_ptr, "edge_ptr", torch.int64),
+                        (seg_rel, "seg_rel", torch.int32), (wrap_mask, "wrap_mask", torch.int32),
+                        (rows, "rows", torch.int32), (cols, "cols", torch.int32)):
+        if tns is None and nm in ("wrap_mask", "rows", "cols"):
+            continue
+        if not isinstance(tns, torch.Tensor):
+            raise TypeError(f"{nm}: expected a torch.Tensor, got {type(tns).__name__}")
+        if tns.dtype != dt:
+            raise TypeError(f"{nm}: dtype {tns.dtype}, expected {dt}")
+        if not tns.is_contiguous():
+            raise ValueError(f"{nm}: must be contiguous")
+    if edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError("epoch_batch: edges must be [n_edges, 2]")
+    K = edge_ptr.numel() - 1
+    if edge_ptr.dim() != 1 or K < 1:
+        raise ValueError("epoch_batch: edge_ptr must have K + 1 >= 2 entries")
+    if seg_rel.dim() != 1:
+        raise ValueError("epoch_batch: seg_rel must be [n_seg]")
+    if wrap_mask is not None and wrap_mask.numel() < -(-K // 32):
+        raise ValueError("epoch_batch: wrap_mask must hold one bit per relation")
+    for v, nm, hi in ((batch, "batch", 2**31), (t, "t", 2**31), (epoch, "epoch", 2**32),
+                      (first_slot, "first_slot", 2**31 - K), (bad_row, "bad_row", 2**31)):
+        if int(v) != v or not (1 if nm == "batch" else 0) <= int(v) < hi:
+            raise ValueError(f"epoch_batch: {nm} = {v!r} out of range")
+    n_seg = seg_rel.numel()
+    n = n_seg * int(batch)
+    if n > 2**31 - 257:
+        raise ValueError("epoch_batch: too many pairs")
+    for o, nm in ((rows, "rows"), (cols, "cols")):
+        if o is not None and o.numel() != n:
+            raise ValueError(f"epoch_batch: {nm} must have n_seg·batch = {n} entries")
+    for tns, nm in ((edges, "edges"), (edge_ptr, "edge_ptr"), (seg_rel, "seg_rel"), (wrap_mask, "wrap_mask"),
+                    (rows, "rows"), (cols, "cols")):
+        if tns is not None and not tns.is_cuda:
+            raise ValueError(f"{nm}: must be a device (HIP) tensor")
+    if rows is None or cols is None:
+        buf = torch.empty((2, n), device=edges.device, dtype=torch.int32)
+        rows = buf[0] if rows is None else rows
+        cols = buf[1] if cols is None else cols
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None  # noqa: E731
+    check(_lib.load().dg_epoch_batch_i32(ptr(edges), edges.shape[0], edge_ptr.data_ptr(), K, ptr(seg_rel), n_seg,
+                                         ptr(wrap_mask), int(batch), int(t), int(epoch), int(seed) & (2**64 - 1),
+                                         int(first_slot), int(bad_row), ptr(rows), ptr(cols), _stream_ptr(stream)),
+          "dg_epoch_batch_i32")
+    return rows, cols
+
+
 def slot_score_hinge_bf16(E_row: torch.Tensor, E_col: torch.Tensor, pos_rows: torch.Tensor, pos_cols: torch.Tensor,
                           table: torch.Tensor, slot0: int, n_slots: int, batch: int, seed: int, G: torch.Tensor,
                           D: torch.Tensor, margin: float, out: torch.Tensor, neg_rows: torch.Tensor,

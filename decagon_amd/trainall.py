@@ -14,24 +14,25 @@ scorer launch over the positive and negative pairs (dg_decoder_score_seg_f32), o
 row reductions into dE (dg_segment_rows_sum_f32 over node-major occurrence lists, built by
 one stable device sort each).  The forward, the TrainPlan, the dropout masks, the embeddings
 tables and the Adam slots are those of `opt_op`, so all-relation steps and ordinary steps mix.
+
+The batches are host dicts, packed and uploaded per step, or an epochs.DeviceBatches formed on the
+device from resident edges (epochs.EdgeBatches), which the step uses as it is; `train_epoch_all`
+runs an epoch of the latter.
 """
 from __future__ import annotations
 
-from typing import Dict, Mapping, Optional, Tuple
+import time
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import kernels
+from .epochs import DeviceBatches, _items
 from .evaluate import _stacked_latents
 from .graph import InvalidArgumentError, Node, RunContext
 
 EdgeType = Tuple[int, int]
-
-
-def _items(per_rel):
-    """(relation, array) pairs of a mapping, or of a sequence of such pairs."""
-    return list(per_rel.items()) if isinstance(per_rel, Mapping) else [(k, v) for k, v in per_rel]
 
 
 def pack_batches(batches, edge_types, shapes) -> Dict[EdgeType, Dict[str, np.ndarray]]:
@@ -130,6 +131,74 @@ def _alias_stack(ctx: RunContext, opt, et: EdgeType, first: int, K: int) -> torc
     return cache[key]
 
 
+stage_log: Optional[dict] = None  # a dict here collects the step's stages in ms (scripts/epoch_bench.py)
+
+
+def _stage(name: str, t0: float) -> float:
+    """With `stage_log` set: synchronise, add the host time since t0 to stage `name`, return now."""
+    if stage_log is None:
+        return t0
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    stage_log[name] = stage_log.get(name, 0.0) + 1e3 * (t1 - t0)
+    return t1
+
+
+def _device_view(batches: DeviceBatches, edge_types) -> Dict[EdgeType, dict]:
+    """A DeviceBatches in pack_batches' terms: the host seg_ptr / seg_rel (K small ints, what the
+    checks and fed negatives read) and the device arrays under "dev"."""
+    out = {}
+    for et, tb in batches.items():
+        if et not in edge_types:
+            raise ValueError(f"unknown edge type {et}")
+        if tb.n_seg > edge_types[et] or (tb.n_seg and int(tb.rel_host.max()) >= edge_types[et]):
+            raise ValueError(f"edge type {et}: the batches list relations it does not have")
+        out[et] = {"seg_ptr": np.arange(tb.n_seg + 1, dtype=np.int64) * batches.batch_size, "seg_rel": tb.rel_host,
+                   "dev": tb}
+    return out
+
+
+def _decoder_meta(ctx: RunContext, opt, model, et: EdgeType) -> dict:
+    """What a step derives from an edge type's unchanging decoder layout, per (optimizer, edge type)
+    in the session cache: the global slot of its first relation, the set of its latent nodes, and
+    the offsets of the variables' gradient slices in the decoder's flat buffer — in place of a walk
+    over dec.latent(k) for all K every step.  Rebuilt if the flat buffer moved."""
+    key = ("trainall_meta", id(opt), et)
+    cache = ctx.session.caches
+    dec = model.edge_type2decoder[et]
+    meta = cache.get(key)
+    if meta is None or meta["flat_ptr"] != dec.flat.data_ptr():
+        ets = list(model.edge_types)
+        K = model.edge_types[et]
+        first = sum(model.edge_types[t] for t in ets[:ets.index(et)])
+        specs = [dec.latent(k) for k in range(K)]
+        gk, lk = specs[0][0], specs[0][2]
+        off = lambda c: (specs[0][c].tensor.data_ptr() - dec.flat.data_ptr()) // 4  # noqa: E731
+        slices = {}
+        if gk == "dense":
+            shared = all(sp[1] is specs[0][1] for sp in specs)
+            slices["dG"] = (off(1), 1 if shared else K)
+        elif gk == "diag":
+            slices["dG_diag"] = (off(1), K)
+        if lk == "diag":
+            slices["dl"] = (off(3), K)
+        lat = frozenset(opt.latent_inters[first:first + K]) | frozenset(opt.latent_varies[first:first + K])
+        meta = cache[key] = {"flat_ptr": dec.flat.data_ptr(), "first": first, "latents": lat,
+                             "grad_slices": slices, "views": gk == "dense"}
+    return meta
+
+
+def _cached_latents(ctx: RunContext, meta: dict, dec, d: int):
+    """_stacked_latents, kept across steps where (G, l) are views of the decoder's flat buffer
+    (DEDICOM, Bilinear: the optimizer updates it in place); the expanded forms depend on the
+    variables' values and are rebuilt per run."""
+    if not meta["views"]:
+        return _stacked_latents(ctx, dec, d)
+    if meta.get("Gl_d") != d:
+        meta["Gl"], meta["Gl_d"] = _stacked_latents(ctx, dec, d), d
+    return meta["Gl"]
+
+
 def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None, apply: bool = True):
     """One step on Σ_(i,j) Σ_k hinge cost of relation k's batch (module docstring).
 
@@ -145,13 +214,23 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
     once); returns the cost (float, before the update).  apply=False: (cost, grads_vars) with
     grads_vars exactly as `opt.grads_vars` returns it, nothing updated.
 
+    batches may also be an epochs.DeviceBatches (EdgeBatches.batch): the step then uses its device
+    arrays as they are — nothing is packed, no index array is uploaded (fed negatives apart) and
+    nothing is read back before the cost — and takes the decoder's operand views and gradient
+    slices from a per-(optimizer, edge type) cache in place of a walk over every relation's
+    variables.  It runs the same kernels on the same indices: cost and gradients equal the host
+    form's on EdgeBatches.host_batch bit for bit.
+
     NotImplementedError for a sharded session; InvalidArgumentError when a decoder latent of a
     trained edge type, or `outputs` / `neg_outputs` / `cost`, is fed."""
     model = opt._model()
     if getattr(sess, "shard", None) is not None:
         raise NotImplementedError("train_step_all runs on one GPU (the session is sharded)")
     shapes = {et: tuple(int(x) for x in opt.edge_type2dim[et][0]) for et in model.edge_types}
-    packed = pack_batches(batches, model.edge_types, shapes)
+    if isinstance(batches, DeviceBatches):
+        packed = _device_view(batches, model.edge_types)
+    else:
+        packed = pack_batches(batches, model.edge_types, shapes)
     if neg_samples is None:
         for et, p in packed.items():
             if len(set(np.diff(p["seg_ptr"]).tolist())) > 1:
@@ -167,7 +246,13 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
         for nd in (opt.outputs, opt.neg_outputs, opt.cost):
             if ctx.is_fed(nd):
                 raise InvalidArgumentError(f"{nd.name} is fed: the cost's gradient does not reach the model")
-        for et in packed:
+        t0 = time.perf_counter()
+        for et, p in packed.items():
+            if "dev" in p:  # (the cached set of the edge type's latent nodes against the few feeds)
+                lat = _decoder_meta(ctx, opt, model, et)["latents"]
+                if any(nd in lat for nd in ctx.feeds):
+                    raise InvalidArgumentError("train_step_all trains the decoder's variables; a latent matrix is fed")
+                continue
             first = sum(model.edge_types[t] for t in ets[:ets.index(et)])
             for r in range(first, first + model.edge_types[et]):
                 if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
@@ -177,6 +262,7 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
             raise NotImplementedError("train_step_all runs on one GPU (the plan is sharded)")
         dev = ctx.session.device
         dec_grads = opt._decoder_grad_buffers(ctx, model)
+        t0 = _stage("forward", t0)
         costs, work = [], []
         for et, p in packed.items():
             i, j = et
@@ -187,21 +273,30 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
             dec = model.edge_type2decoder[et]
             row_t, col_t = opt._tables(ctx, i, j)
             d = row_t.shape[1]
-            G, l = _stacked_latents(ctx, dec, d)
             fed = negs_host is not None
-            # one upload: [rows | cols | (negatives) | seg_ptr | seg_ptr + n | seg_rel | seg_rel]
-            host = np.concatenate([p["rows"], p["cols"]] + ([negs_host[et]] if fed else []) +
-                                  [p["seg_ptr"], p["seg_ptr"][1:] + n, p["seg_rel"], p["seg_rel"]]).astype(np.int32)
-            buf = torch.from_numpy(host).to(dev)
-            rows, cols = buf[:n], buf[n:2 * n]
-            o = 3 * n if fed else 2 * n
-            seg2, o = buf[o:o + 2 * n_seg + 1], o + 2 * n_seg + 1
-            rel2 = buf[o:o + 2 * n_seg]
-            seg_ptr, seg_rel = seg2[:n_seg + 1], rel2[:n_seg]
-            if fed:
-                negs = buf[2 * n:3 * n]
+            tb = p.get("dev")
+            if tb is not None:
+                meta = _decoder_meta(ctx, opt, model, et)
+                G, l = _cached_latents(ctx, meta, dec, d)
+                rows, cols, seg2, rel2, seg_ptr, seg_rel = tb.rows, tb.cols, tb.seg2, tb.rel2, tb.seg_ptr, tb.seg_rel
+                if fed:
+                    negs = torch.from_numpy(negs_host[et]).to(dev)
             else:
-                first = sum(model.edge_types[t] for t in ets[:ets.index(et)])
+                G, l = _stacked_latents(ctx, dec, d)
+                # one upload: [rows | cols | (negatives) | seg_ptr | seg_ptr + n | seg_rel | seg_rel]
+                host = np.concatenate([p["rows"], p["cols"]] + ([negs_host[et]] if fed else []) +
+                                      [p["seg_ptr"], p["seg_ptr"][1:] + n, p["seg_rel"], p["seg_rel"]]).astype(np.int32)
+                buf = torch.from_numpy(host).to(dev)
+                rows, cols = buf[:n], buf[n:2 * n]
+                o = 3 * n if fed else 2 * n
+                seg2, o = buf[o:o + 2 * n_seg + 1], o + 2 * n_seg + 1
+                rel2 = buf[o:o + 2 * n_seg]
+                seg_ptr, seg_rel = seg2[:n_seg + 1], rel2[:n_seg]
+                if fed:
+                    negs = buf[2 * n:3 * n]
+            t0 = _stage("operands", t0)
+            if not fed:
+                first = meta["first"] if tb is not None else sum(model.edge_types[t] for t in ets[:ets.index(et)])
                 s = opt._sampler(ctx)
                 stack = _alias_stack(ctx, opt, et, first, K)
                 if stack.shape[1] > row_t.shape[0]:
@@ -211,30 +306,37 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
                 tabs = stack.index_select(0, seg_rel.long()).contiguous()
                 negs = kernels.unigram_sample_slots(tabs, slot0, nk, n, opt.seed, first_slot=slot0)
                 s.counter = (slot0 + n_seg) * nk
+            t0 = _stage("sampler", t0)
             # positives, then negatives (the positive batch's columns: optimizer.py:51-57)
             scores = kernels.decoder_score_seg(row_t, col_t, torch.cat([rows, negs]), torch.cat([cols, cols]), seg2,
                                                G, l, seg_rel=rel2)
             pos, neg = scores[:n], scores[n:]
             costs.append(kernels.hinge_loss(pos, neg, opt.margin, workspace=kernels.hinge_workspace(dev)))
+            t0 = _stage("score_hinge", t0)
             gflat = dec_grads[et]
             outs = {"dG": None, "dl": None, "dG_diag": None}
-            specs = [dec.latent(k) for k in range(K)]
-            gk, lk = specs[0][0], specs[0][2]
+            if tb is not None:  # the slices of gflat, from the cached offsets
+                for nm, (off, per) in meta["grad_slices"].items():
+                    outs[nm] = gflat[off:off + per * (d * d if nm == "dG" else d)]
+            else:
+                specs = [dec.latent(k) for k in range(K)]
+                gk, lk = specs[0][0], specs[0][2]
 
-            def stacked(c, per):  # the K variables' gradient slices as one [K, per] view of gflat
-                off0 = (specs[0][c].tensor.data_ptr() - dec.flat.data_ptr()) // 4
-                return gflat[off0:off0 + K * per]
+                def stacked(c, per):  # the K variables' gradient slices as one [K, per] view of gflat
+                    off0 = (specs[0][c].tensor.data_ptr() - dec.flat.data_ptr()) // 4
+                    return gflat[off0:off0 + K * per]
 
-            if gk == "dense":
-                shared = all(sp[1] is specs[0][1] for sp in specs)
-                outs["dG"] = opt._grad_view(dec, gflat, specs[0][1]) if shared else stacked(1, d * d)
-            elif gk == "diag":
-                outs["dG_diag"] = stacked(1, d)
-            if lk == "diag":
-                outs["dl"] = stacked(3, d)
+                if gk == "dense":
+                    shared = all(sp[1] is specs[0][1] for sp in specs)
+                    outs["dG"] = opt._grad_view(dec, gflat, specs[0][1]) if shared else stacked(1, d * d)
+                elif gk == "diag":
+                    outs["dG_diag"] = stacked(1, d)
+                if lk == "diag":
+                    outs["dl"] = stacked(3, d)
             op = kernels.PreparedDecoderGradSeg(row_t, col_t, rows, cols, negs, seg_ptr, seg_rel, pos, neg, G, l,
                                                 opt.margin, **outs)
             work.append((i, j, n, rows, cols, negs, op))
+            t0 = _stage("gradient_setup", t0)
 
         def decoder_grad(dE):
             for i, j, n, rows, cols, negs, op in work:
@@ -246,12 +348,28 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
                 kernels.segment_rows_sum(node_ptr, order, op.grad_cols, dE[j])
 
         tp.backward(decoder_grad)
+        t0 = _stage("backward", t0)
         # (the edge types' sums are added on the host, in float64)
         cost = torch.cat([c.reshape(1) for c in costs]) if costs else torch.zeros(1, device=dev)
-        return cost, opt._finish_step(ctx, model, tp, dec_grads, apply)
+        out = cost, opt._finish_step(ctx, model, tp, dec_grads, apply)
+        _stage("update", t0)
+        return out
 
     node = Node("trainall/step", fn)
     node.training = True
     cost, gv = sess.run(node, feed_dict=dict(feed_dict))
     cost = float(np.asarray(cost, np.float64).sum())
     return cost if apply else (cost, gv)
+
+
+def train_epoch_all(sess, opt, placeholders, feed_dict, eb, epoch: int, neg_samples=None) -> np.ndarray:
+    """One epoch of all-relation steps from an epochs.EdgeBatches: steps 0 .. eb.steps(epoch) − 1,
+    each `train_step_all` on `eb.batch(epoch, t)` (applied).  neg_samples: None (device-drawn
+    negatives), or a callable (t, DeviceBatches) → the step's fed negatives.  Returns the steps'
+    costs as a float64 array."""
+    costs = []
+    for t in range(eb.steps(epoch)):
+        db = eb.batch(epoch, t)
+        negs = neg_samples(t, db) if neg_samples is not None else None
+        costs.append(train_step_all(sess, opt, placeholders, feed_dict, db, neg_samples=negs))
+    return np.asarray(costs, np.float64)

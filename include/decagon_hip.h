@@ -42,7 +42,9 @@ extern "C" {
  * the host helper dg_seg_tile_lookup (evaluation of all relations of an edge type in one pass);
  * dg_decoder_grad_seg_workspace, dg_decoder_grad_seg_f32, dg_segment_rows_sum_f32 and the host
  * helpers dg_segment_rows_sum_chunk / dg_segment_rows_sum_waves (the decoder backward of every
- * relation's batch of an edge type in one pass). */
+ * relation's batch of an edge type in one pass); dg_epoch_batch_i32 and the host helpers
+ * dg_epoch_perm_host / dg_epoch_key_host (a step's batches of every relation from device-resident
+ * edges in the epoch's shuffled order). */
 int32_t dg_abi_version(void);
 
 /* --------------------------------------------------------------------------------------
@@ -1154,6 +1156,42 @@ int dg_unigram_sample(const uint32_t* alias_table, int32_t range, int32_t n, uin
 int dg_unigram_sample_slots(const uint32_t* alias_table, int32_t range, int64_t alias_stride,
                             int32_t slot0, int32_t batch, int32_t n, uint64_t seed, int32_t* out,
                             void* stream);
+
+/* --------------------------------------------------------------------------------------
+ * One step's batches of every relation of an edge type, from device-resident training edges in
+ * the epoch's shuffled order (csrc/epochs.hip, csrc/permute.h; additive to ABI 39).
+ * Replaces EdgeMinibatchIterator.shuffle and .next_minibatch_feed_dict's batch slicing
+ * (decagon/deep/minibatch.py:278-322).
+ *
+ * edges: the edge type's training edges, relation-major, interleaved (row, col) int32 pairs
+ * [n_edges x 2], 8-byte aligned; edge_ptr int64 [n_rel + 1]: relation k's edges are
+ * [edge_ptr[k], edge_ptr[k+1]), n_k of them (< 2^31); seg_rel int32 [n_seg]; wrap_mask: bit
+ * (k & 31) of word k >> 5 set when relation k wraps round, or NULL (none does).  For segment s,
+ * k = seg_rel[s], nb = n_k / batch (rounded down), tb = t mod nb if k wraps, else t, and c in
+ * [0, batch):
+ *
+ *     (rows, cols)[s*batch + c] = edges[edge_ptr[k] + perm(n_k, key, tb*batch + c)],
+ *     key = epoch_key(seed, epoch, first_slot + k)                       (permute.h)
+ *
+ * A segment without a batch — nb == 0, tb >= nb without wrapping, k outside [0, n_rel), or an
+ * edge_ptr entry outside [0, n_edges] — reads no edge: its rows are `bad_row` (pass the row
+ * table's length: the segmented kernels skip such pairs) and its columns 0.  Exactly
+ * n_seg*batch entries of rows and of cols are written.  Asynchronous; n_seg == 0 succeeds
+ * without a launch.  Rejected on the host before any HIP call: DG_EINVAL for a NULL edge_ptr,
+ * (n_edges > 0) NULL edges, (n_seg > 0) NULL seg_rel, rows or cols, n_rel < 1, n_edges < 0,
+ * batch <= 0, n_seg < 0, t < 0, first_slot < 0, n_seg*batch > 2^31 - 257; DG_EALIGN for
+ * edges or edge_ptr not 8-byte aligned, or seg_rel, wrap_mask, rows or cols not 4-byte aligned.
+ *
+ * dg_epoch_perm_host / dg_epoch_key_host: permute.h's perm (out[i] = perm(n, key, x[i]);
+ * DG_EINVAL for n < 1, count < 0, a NULL array or an x[i] outside [0, n)) and epoch_key on the
+ * host, for tests of the numpy restatement (decagon_amd/epochs.py).
+ * -------------------------------------------------------------------------------------- */
+int dg_epoch_batch_i32(const int32_t* edges, int64_t n_edges, const int64_t* edge_ptr, int32_t n_rel,
+                       const int32_t* seg_rel, int32_t n_seg, const uint32_t* wrap_mask, int32_t batch,
+                       int32_t t, uint32_t epoch, uint64_t seed, int32_t first_slot, int32_t bad_row,
+                       int32_t* rows, int32_t* cols, void* stream);
+int dg_epoch_perm_host(int32_t n, uint32_t key, const int32_t* x, int32_t* out, int64_t count);
+uint32_t dg_epoch_key_host(uint64_t seed, uint32_t epoch, uint32_t slot);
 
 #ifdef __cplusplus
 }
