@@ -47,6 +47,20 @@ inline int lanes_per_row(int d) {
     return lp;
 }
 
+typedef float f32x16 __attribute__((ext_vector_type(16)));  // the accumulator of v_mfma_f32_32x32x2_f32
+
+// Row of the 32×32 tile that accumulator register r (0..15) of lane half h (lane >> 5) holds; the
+// lane's column is lane & 31.
+__device__ __forceinline__ constexpr int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// x[0..4) = the components of v: a float4 load unpacked into a per-lane array
+__device__ __forceinline__ void put4(float* x, const float4& v) {
+    x[0] = v.x;
+    x[1] = v.y;
+    x[2] = v.z;
+    x[3] = v.w;
+}
+
 __device__ __forceinline__ void fma4(float4& acc, float s, const float4& x) {
     acc.x = fmaf(s, x.x, acc.x);
     acc.y = fmaf(s, x.y, acc.y);

@@ -42,7 +42,8 @@ __global__ __launch_bounds__(256) void decoder_score_kernel(const DecArgs a) {
     score_tile(a.t, valid ? a.row_idx[p] : 0, valid ? a.col_idx[p] : 0, valid, part);
     if ((i & 1) == 0) {  // lane 2r holds score r of its half
         const int r = i >> 1;
-        const int pp = p0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int pp = p0 + (r & 3) + 8 * (r >> 2) + 4 * h;  // p0 + dg::acc_row(r, h): r is not a constant here, and
+                                                             // this association keeps the kernel's validated code
         if (pp < a.n_pairs) a.out[pp] = part[0];
     }
 }
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(128) void decoder_hinge_kernel(const HingeArgs a) {
     score_tile(a.t, ridx, cidx, valid, part);
     if ((i & 1) == 0) {  // lane 2r holds score r of its half
         const int r = i >> 1;
-        const int q = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int q = dg::acc_row(r, h);
         const float v = (b0 + q < a.n) ? part[0] : 0.f;
         sc[side][q] = v;
         if (b0 + q < a.n) (side == 0 ? a.pos : a.neg)[b0 + q] = v;

@@ -9,8 +9,6 @@
 
 namespace dg {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -77,7 +75,7 @@ __device__ __forceinline__ float4 ld_emb4(const float* p) {
 // past the end.  T = (U∘l)·G runs on v_mfma_f32_32x32x2_f32 in k-blocks of 32 whose A/B
 // fragments are loaded up front (one memory round trip per block, not per k-step); then
 // score[p] = Σ_j T[p][j]·l[j]·V[p][j] is folded over the 32 lanes of each half-wave.
-// Returns the score of pair (r&3)+8(r>>2)+4h, r = (lane & 31) >> 1, in part[0] of lanes 2r and
+// Returns the score of pair acc_row(r, h), r = (lane & 31) >> 1, in part[0] of lanes 2r and
 // 2r+1 of each half (a reduce-scatter over the half's 32 lanes: 16 shuffles instead of a
 // butterfly per score's 80).  kSc1: every load of
 // row_table / col_table is an sc1 load (the tables were written in this launch).  kD: the width
@@ -157,7 +155,7 @@ __device__ __forceinline__ void score_tile(const DecTab& t, int ridx, int cidx, 
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int prow = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int prow = acc_row(r, h);
             v[r] = ld_emb<kSc1>(t.col_table + (int64_t)__shfl(cidx, prow) * t.ld_col + i);
         }
         if (t.l) {
@@ -205,7 +203,7 @@ __device__ __forceinline__ void score_tile(const DecTab& t, int ridx, int cidx, 
         float v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int prow = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int prow = acc_row(r, h);
             const int c = __shfl(cidx, prow);  // lane prow names pair prow
             v[r] = ld_emb<kSc1>(t.col_table + (int64_t)c * t.ld_col + j);
         }

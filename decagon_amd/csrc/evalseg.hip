@@ -28,6 +28,7 @@
 #include "common.h"
 #include "decoder_tile.h"
 #include "rank_metrics.h"
+#include "rel_operands.h"
 #include "segmap.h"
 
 namespace {
@@ -35,14 +36,14 @@ namespace {
 using dg::DecTab;
 
 struct SegScoreArgs {
-    DecTab t;  // G, l: relation 0's
+    DecTab t;  // (G, l: relation 0's, as in ops)
+    dg::RelOps ops;
     const int32_t* row_idx;
     const int32_t* col_idx;
     const int32_t* seg_ptr;
     const int32_t* seg_rel;
     float* out;
-    int64_t g_stride, l_stride;
-    int32_t n_rows, n_cols, n_seg, n_pairs, n_rel, n_tiles;
+    int32_t n_rows, n_cols, n_seg, n_pairs, n_tiles;
 };
 
 // Pairs whose index lies outside the tables, and segments whose relation lies outside [0, n_rel),
@@ -54,18 +55,16 @@ __global__ __launch_bounds__(256) void decoder_score_seg_kernel(const SegScoreAr
     int s, local;
     if (!dg::seg_tile_find(a.seg_ptr, a.n_seg, 32, vt, s, local)) return;
     s = __builtin_amdgcn_readfirstlane(s);
-    const int beg = a.seg_ptr[s];
-    int end = a.seg_ptr[s + 1];
-    if (end > a.n_pairs) end = a.n_pairs;
+    int beg, end;
+    if (!dg::seg_bounds(a.seg_ptr, a.n_pairs, s, beg, end)) return;
     const int p0 = beg + local * 32;
-    if (beg < 0 || beg >= end || p0 >= end) return;
-    int k = a.seg_rel ? a.seg_rel[s] : s;
-    k = __builtin_amdgcn_readfirstlane(k);
-    const bool rel_ok = k >= 0 && k < a.n_rel;
+    if (p0 >= end) return;
+    int k;
+    const bool rel_ok = dg::seg_relation(a.seg_rel, a.ops.n_rel, s, k);
     if (!rel_ok) k = 0;
     DecTab t = a.t;
-    t.G += (int64_t)k * a.g_stride;
-    if (t.l) t.l += (int64_t)k * a.l_stride;
+    t.G = dg::rel_G(a.ops, k);
+    t.l = dg::rel_l(a.ops, k);
 
     const int i = lane & 31;
     const int h = lane >> 5;
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(256) void decoder_score_seg_kernel(const SegScoreAr
     dg::score_tile(t, r, c, in_seg && ok, part);
     // lane 2q holds score q of its half; the pair it belongs to is named by lane `slot`
     const int q = i >> 1;
-    const int slot = (q & 3) + 8 * (q >> 2) + 4 * h;
+    const int slot = dg::acc_row(q, h);
     const int slot_ok = __shfl((int)ok, slot);
     if ((i & 1) == 0) {
         const int pp = p0 + slot;
@@ -191,13 +190,10 @@ extern "C" int dg_decoder_score_seg_f32(const float* row_table, int64_t ld_row, 
     if (!row_table || !col_table || !seg_ptr || !G) return DG_EINVAL;
     if (n_pairs > 0 && (!row_idx || !col_idx || !out)) return DG_EINVAL;
     if (n_rows < 1 || n_cols < 1 || ld_row < d || ld_col < d) return DG_EINVAL;
-    if (g_stride != 0 && g_stride != (int64_t)d * d) return DG_EINVAL;
-    if (l && l_stride != 0 && l_stride != d) return DG_EINVAL;
-    const bool per_rel = g_stride != 0 || (l && l_stride != 0);
-    if (seg_rel ? n_rel <= 0 : (per_rel && n_seg > n_rel)) return DG_EINVAL;
+    SegScoreArgs a{};
+    if (dg::rel_ops(G, g_stride, l, l_stride, n_rel, d, seg_rel != nullptr, n_seg, a.ops) != DG_OK) return DG_EINVAL;
     if ((int64_t)n_pairs + 32LL * n_seg >= (1ll << 31)) return DG_EINVAL;  // 32-bit pair offsets
     if (n_pairs == 0) return DG_OK;
-    SegScoreArgs a{};
     a.t = DecTab{row_table, col_table, G, l, ld_row, ld_col, d,
                  dg::aligned16(row_table) && (ld_row & 3) == 0 && (!l || dg::aligned16(l))};
     a.row_idx = row_idx;
@@ -205,13 +201,10 @@ extern "C" int dg_decoder_score_seg_f32(const float* row_table, int64_t ld_row, 
     a.seg_ptr = seg_ptr;
     a.seg_rel = seg_rel;
     a.out = out;
-    a.g_stride = g_stride;
-    a.l_stride = l ? l_stride : 0;
     a.n_rows = n_rows;
     a.n_cols = n_cols;
     a.n_seg = n_seg;
     a.n_pairs = n_pairs;
-    a.n_rel = seg_rel ? n_rel : n_seg;  // (without a map segment s is relation s)
     a.n_tiles = (int32_t)dg::seg_tile_grid(n_pairs, n_seg, 32);
     hipLaunchKernelGGL(decoder_score_seg_kernel, dim3(dg::ceil_div(a.n_tiles, 4)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), a);

@@ -21,7 +21,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using dg::f32x16;
 
 struct GemmOne {
     const float* a;
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void gemm_f32_generic(const GemmArgs args) {
             // (bb = b_map[b]: a relation shard's batch b is global relation bb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int mrow = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int mrow = tm * 32 + dg::acc_row(r, h);
                 const uint32_t idx = static_cast<uint32_t>(((int64_t)bb * g.m + mrow) * g.n + col);
                 dsum[r] += t[r] * dg::keep_scale(dkey, idx, g.drop_keep);
             }
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void gemm_f32_generic(const GemmArgs args) {
             float* C = g.c + (g.reduce ? bblk : bb) * g.c_bs + (int64_t)col * g.c_sn;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int mrow = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int mrow = tm * 32 + dg::acc_row(r, h);
                 if (mrow < g.m) C[(int64_t)mrow * g.c_sm] = acc[r] * s;
             }
         }
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void gemm_f32_reduce_k32(const GemmArgs args) 
             for (int t = 0; t < NT; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int mrow = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int mrow = tm * 32 + dg::acc_row(r, h);
                     const uint32_t idx = static_cast<uint32_t>(((int64_t)bb * g.m + mrow) * g.n + t * 32 + i);
                     sum[t][r] += acc[t][r] * dg::keep_scale(dkey, idx, g.drop_keep);
                 }
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void gemm_f32_reduce_k32(const GemmArgs args) 
         float* C = g.c + bblk * g.c_bs + (int64_t)col * g.c_sn;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int mrow = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int mrow = tm * 32 + dg::acc_row(r, h);
             if (mrow < g.m) C[(int64_t)mrow * g.c_sm] = sum[t][r];
         }
     }
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(256) void gemm_f32_resident_a(const GemmArgs args) 
             float* C = g.c + bb * g.c_bs + (int64_t)col * g.c_sn;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int mrow = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int mrow = tm * 32 + dg::acc_row(r, h);
                 if (mrow < g.m) C[(int64_t)mrow * g.c_sm] = acc[r] * s_col;
             }
         }
@@ -495,7 +495,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const TnArgs a) {
         const int q = e >> 10, r = (e >> 6) & 15, l = e & 63;
         const float v = red[0][q][r][l] + red[1][q][r][l];
         const int mt = q / NT, nt = q - mt * NT;
-        const int row = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
+        const int row = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);  // (dg::acc_row, as decoder.hip spells it)
         out[(int64_t)row * a.N + nt * 32 + (l & 31)] = v;
     }
 }

@@ -26,11 +26,12 @@
 // one workgroup per output row, the list split over the waves in fixed chunks and the waves'
 // sums combined in a fixed tree.  No float atomics anywhere: results are bitwise reproducible.
 #include "common.h"
+#include "rel_operands.h"
 #include "segmap.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using dg::f32x16;
 
 struct GradSegArgs {
     const float* row_table;
@@ -42,34 +43,18 @@ struct GradSegArgs {
     const int32_t* seg_rel;
     const float* pos;
     const float* neg;
-    const float* G;  // relation 0's
-    const float* l;
+    dg::RelOps ops;
     float* mv;
     float* grad_cols;
     float* dM;  // [n_seg][d][d]
     float* dG;
     float* dl;
     float* dG_diag;
-    int64_t ld_row, ld_col, g_stride, l_stride;
-    int32_t n_rows, n_cols, n_seg, n_pairs, n_rel, n_tiles;
+    int64_t ld_row, ld_col;
+    int32_t n_rows, n_cols, n_seg, n_pairs, n_tiles;
     float margin;
     int32_t pad;
 };
-
-// [beg, end) of segment s, end clamped to the pair count; false for an empty or malformed one
-__device__ __forceinline__ bool seg_bounds(const GradSegArgs& a, int s, int& beg, int& end) {
-    beg = a.seg_ptr[s];
-    end = a.seg_ptr[s + 1];
-    if (end > a.n_pairs) end = a.n_pairs;
-    return beg >= 0 && beg < end;
-}
-
-// relation of segment s; false when it lies outside [0, n_rel)
-__device__ __forceinline__ bool seg_relation(const GradSegArgs& a, int s, int& k) {
-    k = a.seg_rel ? a.seg_rel[s] : s;
-    k = __builtin_amdgcn_readfirstlane(k);
-    return k >= 0 && k < a.n_rel;
-}
 
 // Pair p's indices and hinge mask: act = inside the tables and neg − (pos − margin) > 0.  An
 // inactive pair gets index 0 everywhere (a row that exists: loads stay unconditional).
@@ -97,14 +82,14 @@ __global__ __launch_bounds__(256) void grad_seg_pairs_kernel(const GradSegArgs a
     if (!dg::seg_tile_find(a.seg_ptr, a.n_seg, 32, vt, s, local)) return;
     s = __builtin_amdgcn_readfirstlane(s);
     int beg, end;
-    if (!seg_bounds(a, s, beg, end)) return;
+    if (!dg::seg_bounds(a.seg_ptr, a.n_pairs, s, beg, end)) return;
     const int p0 = beg + local * 32;
     if (p0 >= end) return;
     int k;
-    const bool rel_ok = seg_relation(a, s, k);
+    const bool rel_ok = dg::seg_relation(a.seg_rel, a.ops.n_rel, s, k);
     if (!rel_ok) k = 0;
-    const float* G = a.G + (int64_t)k * a.g_stride;
-    const float* l = a.l ? a.l + (int64_t)k * a.l_stride : nullptr;
+    const float* G = dg::rel_G(a.ops, k);
+    const float* l = dg::rel_l(a.ops, k);
 
     const int i = lane & 31;
     const int h = lane >> 5;
@@ -134,13 +119,8 @@ __global__ __launch_bounds__(256) void grad_seg_pairs_kernel(const GradSegArgs a
         float bt[kH], bg[kH];
         const float4* gt4 = reinterpret_cast<const float4*>(G + (int64_t)(n0 + i) * kD + kH * h);
 #pragma unroll
-        for (int j4 = 0; j4 < kH / 4; ++j4) {
-            const float4 g4 = gt4[j4];
-            bt[4 * j4] = g4.x;
-            bt[4 * j4 + 1] = g4.y;
-            bt[4 * j4 + 2] = g4.z;
-            bt[4 * j4 + 3] = g4.w;
-        }
+        for (int j4 = 0; j4 < kH / 4; ++j4)
+            dg::put4(bt + 4 * j4, gt4[j4]);
 #pragma unroll
         for (int j = 0; j < kH; ++j) bg[j] = G[(int64_t)(kH * h + j) * kD + n0 + i];
         f32x16 accv = {}, accd = {};
@@ -152,7 +132,7 @@ __global__ __launch_bounds__(256) void grad_seg_pairs_kernel(const GradSegArgs a
         const float ln = l ? l[n0 + i] : 1.0f;
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int pp = p0 + (q & 3) + 8 * (q >> 2) + 4 * h;
+            const int pp = p0 + dg::acc_row(q, h);
             if (pp < end) {
                 a.mv[(int64_t)pp * kD + n0 + i] = accv[q] * ln;
                 a.grad_cols[(int64_t)pp * kD + n0 + i] = accd[q] * ln;
@@ -175,8 +155,8 @@ __global__ __launch_bounds__(256) void grad_seg_dm_kernel(const GradSegArgs a) {
     const int t = wid - s * kT * kT;
     const int ta = t / kT, tb = t - ta * kT;
     int beg, end, k;
-    const bool live = seg_bounds(a, s, beg, end);
-    const bool rel_ok = seg_relation(a, s, k);
+    const bool live = dg::seg_bounds(a.seg_ptr, a.n_pairs, s, beg, end);
+    const bool rel_ok = dg::seg_relation(a.seg_rel, a.ops.n_rel, s, k);
     f32x16 acc = {};
     if (live && rel_ok) {
 #pragma unroll 1
@@ -203,7 +183,7 @@ __global__ __launch_bounds__(256) void grad_seg_dm_kernel(const GradSegArgs a) {
     float* out = a.dM + (int64_t)s * kD * kD;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-        const int row = ta * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
+        const int row = ta * 32 + dg::acc_row(q, h);
         out[(int64_t)row * kD + tb * 32 + i] = acc[q];
     }
 }
@@ -217,16 +197,16 @@ __global__ __launch_bounds__(256) void grad_seg_vars_kernel(const GradSegArgs a,
     const int s = blockIdx.x / eb;
     const int e = (blockIdx.x - s * eb) * 256 + threadIdx.x;
     int k;
-    if (!seg_relation(a, s, k)) return;
+    if (!dg::seg_relation(a.seg_rel, a.ops.n_rel, s, k)) return;
     const float* dM = a.dM + (int64_t)s * dd;
-    const float* l = a.l ? a.l + (int64_t)k * a.l_stride : nullptr;
-    if (a.dG && a.g_stride != 0 && e < dd) {
+    const float* l = dg::rel_l(a.ops, k);
+    if (a.dG && a.ops.g_stride != 0 && e < dd) {
         const int ra = e / d, cb = e - ra * d;
         a.dG[(int64_t)k * dd + e] = l ? l[ra] * dM[e] * l[cb] : dM[e];
     }
     if (e < d) {  // (the segment's first block)
         if (a.dl) {
-            const float* G = a.G + (int64_t)k * a.g_stride;
+            const float* G = dg::rel_G(a.ops, k);
             float sum = 0.f;
 #pragma unroll 16
             for (int c = 0; c < d; ++c) sum = fmaf(dM[(int64_t)e * d + c] * G[(int64_t)e * d + c], l[c], sum);
@@ -267,11 +247,12 @@ __global__ __launch_bounds__(64 * kSumSlices) void grad_seg_shared_dg_kernel(con
         for (int u = 0; u < kSumBatch; ++u) {
             const int s = sb + u < s1 ? sb + u : s0;  // (clamped: the loads stay unconditional)
             const int k = a.seg_rel ? a.seg_rel[s] : s;
-            ok[u] = sb + u < s1 && k >= 0 && k < a.n_rel;
+            ok[u] = sb + u < s1 && k >= 0 && k < a.ops.n_rel;
             const int kc = ok[u] ? k : 0;
             m[u] = a.dM[(int64_t)s * dd + e];
-            la[u] = a.l ? a.l[(int64_t)kc * a.l_stride + ra] : 1.0f;
-            lb[u] = a.l ? a.l[(int64_t)kc * a.l_stride + cb] : 1.0f;
+            const float* l = dg::rel_l(a.ops, kc);
+            la[u] = l ? l[ra] : 1.0f;
+            lb[u] = l ? l[cb] : 1.0f;
         }
 #pragma unroll
         for (int u = 0; u < kSumBatch; ++u) sum += ok[u] ? la[u] * m[u] * lb[u] : 0.f;
@@ -386,10 +367,8 @@ extern "C" int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, i
     if (!row_table || !col_table || !seg_ptr || !G) return DG_EINVAL;
     if (n_pairs > 0 && (!rows || !cols || !neg_rows || !pos || !neg || !mv || !grad_cols)) return DG_EINVAL;
     if (n_rows < 1 || n_cols < 1 || ld_row < d || ld_col < d) return DG_EINVAL;
-    if (g_stride != 0 && g_stride != (int64_t)d * d) return DG_EINVAL;
-    if (l && l_stride != 0 && l_stride != d) return DG_EINVAL;
-    const bool per_rel = g_stride != 0 || (l && l_stride != 0);
-    if (seg_rel ? n_rel <= 0 : (per_rel && n_seg > n_rel)) return DG_EINVAL;
+    GradSegArgs a{};
+    if (dg::rel_ops(G, g_stride, l, l_stride, n_rel, d, seg_rel != nullptr, n_seg, a.ops) != DG_OK) return DG_EINVAL;
     if (dl && (!l || l_stride != d)) return DG_EINVAL;  // dl[k] is the gradient of a per-relation l_k
     if (dG_diag && g_stride == 0) return DG_EINVAL;     // a per-relation output of a shared G
     const bool vars = dG || dl || dG_diag;
@@ -400,7 +379,6 @@ extern "C" int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, i
         !dg::aligned16(G) || (l && !dg::aligned16(l)) || (vars && !dg::aligned16(workspace)))
         return DG_EALIGN;
     if (n_pairs == 0) return DG_OK;
-    GradSegArgs a{};
     a.row_table = row_table;
     a.col_table = col_table;
     a.rows = rows;
@@ -410,8 +388,6 @@ extern "C" int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, i
     a.seg_rel = seg_rel;
     a.pos = pos;
     a.neg = neg;
-    a.G = G;
-    a.l = l;
     a.mv = mv;
     a.grad_cols = grad_cols;
     a.dM = static_cast<float*>(workspace);
@@ -420,13 +396,10 @@ extern "C" int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, i
     a.dG_diag = dG_diag;
     a.ld_row = ld_row;
     a.ld_col = ld_col;
-    a.g_stride = g_stride;
-    a.l_stride = l ? l_stride : 0;
     a.n_rows = n_rows;
     a.n_cols = n_cols;
     a.n_seg = n_seg;
     a.n_pairs = n_pairs;
-    a.n_rel = seg_rel ? n_rel : n_seg;  // (without a map segment s is relation s)
     a.n_tiles = (int32_t)dg::seg_tile_grid(n_pairs, n_seg, 32);
     a.margin = margin;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -27,6 +27,8 @@
 // with the column as the index: the unique top-k of the row whatever the tiling.
 #include "common.h"
 #include "decoder_tile.h"
+#include "rel_operands.h"
+#include "segmap.h"
 #include "topk_list.h"
 
 namespace {
@@ -50,14 +52,13 @@ inline int slot_chunk(int64_t n_pairs, int64_t n_sel) {
 struct CrossArgs {
     const float* row_table;
     const float* col_table;
-    const float* G;
-    const float* l;
+    dg::RelOps ops;
     const int32_t* row_idx;
     const int32_t* col_idx;
     const int32_t* rel_idx;
     float* out;
-    int64_t ld_row, ld_col, g_stride, l_stride, ld_out;
-    int32_t n_rows, n_cols, n_pairs, n_sel, n_rel, chunk, n_chunks, n_waves, l_vec4;
+    int64_t ld_row, ld_col, ld_out;
+    int32_t n_rows, n_cols, n_pairs, n_sel, chunk, n_chunks, n_waves, l_vec4;
 };
 
 // The B fragments of one d×d G for every (n-block, k-block) of score_tile's loops:
@@ -85,13 +86,7 @@ __device__ __forceinline__ void load_l(const float* l, bool vec4, int i, int h, 
     if (D == 32 && vec4) {
         const float4* l4 = reinterpret_cast<const float4*>(l + 16 * h);
 #pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            const float4 x = l4[s4];
-            w[4 * s4] = x.x;
-            w[4 * s4 + 1] = x.y;
-            w[4 * s4 + 2] = x.z;
-            w[4 * s4 + 3] = x.w;
-        }
+        for (int s4 = 0; s4 < 4; ++s4) dg::put4(w + 4 * s4, l4[s4]);
     } else {
 #pragma unroll
         for (int q = 0; q < D / 2; ++q) w[q] = l[D == 32 ? 16 * h + q : 2 * q + h];
@@ -128,41 +123,34 @@ __global__ __launch_bounds__(256) void score_cross_kernel(const CrossArgs a) {
     const float* up = a.row_table + (int64_t)r * a.ld_row;
     if (D == 32) {
 #pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            const float4 x = *reinterpret_cast<const float4*>(up + 16 * h + 4 * s4);
-            u[4 * s4] = x.x;
-            u[4 * s4 + 1] = x.y;
-            u[4 * s4 + 2] = x.z;
-            u[4 * s4 + 3] = x.w;
-        }
+        for (int s4 = 0; s4 < 4; ++s4) dg::put4(u + 4 * s4, *reinterpret_cast<const float4*>(up + 16 * h + 4 * s4));
     } else {
 #pragma unroll
         for (int q = 0; q < H; ++q) u[q] = up[2 * q + h];
     }
 #pragma unroll
     for (int rr = 0; rr < 16; ++rr) {
-        const int prow = (rr & 3) + 8 * (rr >> 2) + 4 * h;
+        const int prow = dg::acc_row(rr, h);
         const float* vp = a.col_table + (int64_t)__shfl(c, prow) * a.ld_col + i;  // lane prow names pair prow
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) v[nb][rr] = vp[32 * nb];
     }
     float b[D * D / 64];
-    if (!kPerG) load_g<D>(a.G, i, h, b);
+    if (!kPerG) load_g<D>(a.ops.G, i, h, b);
 
     // lane 2q holds score q of its half; the pair it belongs to is named by lane `slot`
     const int q = i >> 1;
-    const int slot = (q & 3) + 8 * (q >> 2) + 4 * h;
+    const int slot = dg::acc_row(q, h);
     const bool slot_ok = __shfl((int)ok, slot) != 0;
 
 #pragma unroll 1
     for (int j = 0; j < cnt; ++j) {
-        int k = a.rel_idx ? a.rel_idx[s0 + j] : s0 + j;
-        k = __builtin_amdgcn_readfirstlane(k);
-        const bool rel_ok = k >= 0 && k < a.n_rel;
+        int k;
+        const bool rel_ok = dg::seg_relation(a.rel_idx, a.ops.n_rel, s0 + j, k);
         if (!rel_ok) k = 0;
         float wl[H], lj[NB];
-        if (kHasL) load_l<D>(a.l + (int64_t)k * a.l_stride, a.l_vec4 != 0, i, h, wl, lj);
-        if (kPerG) load_g<D>(a.G + (int64_t)k * a.g_stride, i, h, b);
+        if (kHasL) load_l<D>(dg::rel_l(a.ops, k), a.l_vec4 != 0, i, h, wl, lj);
+        if (kPerG) load_g<D>(dg::rel_G(a.ops, k), i, h, b);
         float av[H];
 #pragma unroll
         for (int x = 0; x < H; ++x) av[x] = kHasL ? u[x] * wl[x] : u[x];
@@ -197,7 +185,7 @@ __global__ __launch_bounds__(256) void score_cross_kernel(const CrossArgs a) {
 template <int D, bool kPerG>
 void launch_cross_l(const CrossArgs& a, hipStream_t st) {
     const dim3 grid((unsigned)dg::ceil_div(a.n_waves, 4)), block(256);
-    if (a.l)
+    if (a.ops.l)
         hipLaunchKernelGGL((score_cross_kernel<D, kPerG, true>), grid, block, 0, st, a);
     else
         hipLaunchKernelGGL((score_cross_kernel<D, kPerG, false>), grid, block, 0, st, a);
@@ -205,7 +193,7 @@ void launch_cross_l(const CrossArgs& a, hipStream_t st) {
 
 template <int D>
 void launch_cross(const CrossArgs& a, hipStream_t st) {
-    if (a.g_stride)
+    if (a.ops.g_stride)
         launch_cross_l<D, true>(a, st);
     else
         launch_cross_l<D, false>(a, st);
@@ -262,33 +250,25 @@ extern "C" int dg_decoder_score_cross_f32(const float* row_table, int64_t ld_row
     if (n_pairs > 0 && (!row_idx || !col_idx || !out)) return DG_EINVAL;
     if (d != 32 && d != 64) return DG_EINVAL;
     if (ld_row < d || ld_col < d || ld_out < n_sel) return DG_EINVAL;
-    if (g_stride != 0 && g_stride != (int64_t)d * d) return DG_EINVAL;
-    if (l && l_stride != 0 && l_stride != d) return DG_EINVAL;
-    const bool per_rel = g_stride != 0 || (l && l_stride != 0);
-    if (!rel_idx && per_rel && n_sel > n_rel) return DG_EINVAL;
+    CrossArgs a{};
+    if (dg::rel_ops(G, g_stride, l, l_stride, n_rel, d, rel_idx != nullptr, n_sel, a.ops) != DG_OK) return DG_EINVAL;
     if ((int64_t)n_pairs * ld_out >= DG_CROSS_MAX_OUT || n_pairs > INT32_MAX - 64) return DG_EINVAL;  // 32-bit pair offsets
     if (!dg::aligned16(row_table) || !dg::aligned16(col_table) || (ld_row & 3) || (ld_col & 3)) return DG_EALIGN;
     if (n_pairs == 0) return DG_OK;
 
-    CrossArgs a{};
     a.row_table = row_table;
     a.col_table = col_table;
-    a.G = G;
-    a.l = l;
     a.row_idx = row_idx;
     a.col_idx = col_idx;
     a.rel_idx = rel_idx;
     a.out = out;
     a.ld_row = ld_row;
     a.ld_col = ld_col;
-    a.g_stride = g_stride;
-    a.l_stride = l ? l_stride : 0;
     a.ld_out = ld_out;
     a.n_rows = n_rows;
     a.n_cols = n_cols;
     a.n_pairs = n_pairs;
     a.n_sel = n_sel;
-    a.n_rel = rel_idx ? n_rel : (n_sel > n_rel ? n_sel : n_rel);  // (without a map slot s is relation s)
     a.chunk = slot_chunk(n_pairs, n_sel);
     a.n_chunks = dg::ceil_div(n_sel, a.chunk);
     a.n_waves = dg::ceil_div(n_pairs, 32) * a.n_chunks;  // < 2^29 under DG_CROSS_MAX_OUT

@@ -41,4 +41,22 @@ DG_HD inline bool seg_tile_find(const int32_t* ptr, int n_seg, int tile, int vt,
     return (int64_t)local * tile < (int64_t)ptr[lo + 1] - (int64_t)ptr[lo];
 }
 
+#if defined(__HIPCC__)
+// [beg, end) of segment s, end clamped to the element count; false for an empty or malformed one
+__device__ __forceinline__ bool seg_bounds(const int32_t* ptr, int n_total, int s, int& beg, int& end) {
+    beg = ptr[s];
+    end = ptr[s + 1];
+    if (end > n_total) end = n_total;
+    return beg >= 0 && beg < end;
+}
+
+// relation of slot s (map[s], or s itself without a map), wave-uniform; false when it lies
+// outside [0, n_rel)
+__device__ __forceinline__ bool seg_relation(const int32_t* map, int n_rel, int s, int& k) {
+    k = map ? map[s] : s;
+    k = __builtin_amdgcn_readfirstlane(k);
+    return k >= 0 && k < n_rel;
+}
+#endif
+
 }  // namespace dg

@@ -23,11 +23,12 @@
 // exist, so the result is the unique top-k of the relation whatever the tiling, the grid or
 // the order in which waves run.
 #include "common.h"
+#include "rel_operands.h"
 #include "topk_list.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using dg::f32x16;
 
 constexpr int kStripe = 128;  // rows per workgroup: one 32-row block per wave
 constexpr int kWaves = 4;    // waves per workgroup = candidate lists per stripe
@@ -40,7 +41,7 @@ using dg::WaveTopK;
 struct TopkArgs {
     const float* row_table;
     const float* col_table;
-    const float* G;
+    const float* G;  // dg::RelOps's fields, in the order this kernel was measured with
     const float* l;
     const int32_t* ex_rowptr;
     const int32_t* ex_col;
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void topk_stripe_kernel(TopkArgs a) {
             const float lj = l ? l[nb * 32 + i] : 1.0f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int rl = dg::acc_row(r, h);
                 As[(rb * 32 + rl) * LDA + nb * 32 + i] = acc[r] * lj;
             }
         }
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(256) void topk_stripe_kernel(TopkArgs a) {
         const bool cok = c < a.n_cols;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int rl = dg::acc_row(r, h);
             const int row = r0 + rb * 32 + rl;
             const uint32_t exr = (uint32_t)__shfl((int)ex, rl);  // lane rl holds row rl's mask
             bool ok = cok && row < a.n_rows && !((exr >> i) & 1u);
@@ -238,8 +239,8 @@ extern "C" int dg_decoder_topk_f32(const float* row_table, int64_t ld_row, int32
     if (ld_row < d || ld_col < d) return DG_EINVAL;
     if ((uint64_t)n_rows * (uint64_t)n_cols >= (1ull << 32)) return DG_EINVAL;  // 32-bit linear index
     if ((int64_t)n_rel * dg::ceil_div(n_rows, kStripe) >= (1ll << 31)) return DG_EINVAL;
-    if (g_stride != 0 && g_stride != (int64_t)d * d) return DG_EINVAL;
-    if (l && l_stride != 0 && l_stride != d) return DG_EINVAL;
+    dg::RelOps ops;
+    if (dg::rel_ops(G, g_stride, l, l_stride, n_rel, d, false, n_rel, ops) != DG_OK) return DG_EINVAL;
     if ((excl_rowptr == nullptr) != (excl_col == nullptr)) return DG_EINVAL;
     if (flags & ~(DG_TOPK_UPPER | DG_TOPK_NO_DIAG)) return DG_EINVAL;
     if ((flags & DG_TOPK_UPPER) && n_rows != n_cols) return DG_EINVAL;
@@ -252,15 +253,15 @@ extern "C" int dg_decoder_topk_f32(const float* row_table, int64_t ld_row, int32
     TopkArgs a;
     a.row_table = row_table;
     a.col_table = col_table;
-    a.G = G;
-    a.l = l;
+    a.G = ops.G;
+    a.l = ops.l;
     a.ex_rowptr = excl_rowptr;
     a.ex_col = excl_col;
     a.lists = static_cast<uint64_t*>(workspace);
     a.ld_row = ld_row;
     a.ld_col = ld_col;
-    a.g_stride = g_stride;
-    a.l_stride = l ? l_stride : 0;
+    a.g_stride = ops.g_stride;
+    a.l_stride = ops.l_stride;
     a.n_rows = n_rows;
     a.n_cols = n_cols;
     a.n_stripes = dg::ceil_div(n_rows, kStripe);

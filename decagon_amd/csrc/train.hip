@@ -17,7 +17,7 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using dg::f32x16;
 
 constexpr int kPairChunk = 64;   // pairs per dM partial
 
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void decoder_grad_dm_kernel(const float* xw, c
     float* out = part + (int64_t)ch * d * d;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = ta * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int row = ta * 32 + dg::acc_row(r, h);
         out[(int64_t)row * d + tb * 32 + i] = acc[r];
     }
 }

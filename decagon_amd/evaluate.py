@@ -105,6 +105,36 @@ def _stacked_latents(ctx: RunContext, dec, d: int):
     return G, l
 
 
+def first_relation(model, edge_type_ij) -> int:
+    """The flat index (over all edge types, in model.edge_types' order) of relation 0 of an edge type."""
+    ets = list(model.edge_types)
+    return sum(model.edge_types[et] for et in ets[:ets.index(tuple(edge_type_ij))])
+
+
+def _edge_type_decoder(model, edge_type_ij, sigmoid):
+    """The checks of an all-relation query that precede its sess.run; the edge type's decoder."""
+    if sigmoid not in SIGMOID_MODES:
+        raise ValueError(f"sigmoid must be one of {list(SIGMOID_MODES)}")
+    if tuple(edge_type_ij) not in model.edge_type2decoder:
+        raise ValueError(f"unknown edge type {tuple(edge_type_ij)}")
+    return model.edge_type2decoder[tuple(edge_type_ij)]
+
+
+def _edge_type_operands(name, ctx: RunContext, opt, model, edge_type_ij):
+    """All relations of edge type (i, j) inside a run: (K, row table, column table, G, l), G and l
+    as _stacked_latents gives them.  The decoder's variables are read in place, so a fed latent
+    matrix is refused."""
+    i, j = edge_type_ij
+    dec = model.edge_type2decoder[i, j]
+    first = first_relation(model, (i, j))
+    for r in range(first, first + dec.num_types):
+        if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
+            raise ValueError(f"{name} reads the decoder's variables; a latent matrix is fed")
+    row_t, col_t = opt._tables(ctx, i, j)
+    G, l = _stacked_latents(ctx, dec, row_t.shape[1])
+    return dec.num_types, row_t, col_t, G, l
+
+
 def _sigmoid_host(x: np.ndarray, mode: Optional[str]) -> np.ndarray:
     """The reference's score of a float32 logit array (module docstring), on the host."""
     if mode is None:
@@ -133,26 +163,15 @@ def top_candidates(sess, opt, placeholders, feed_dict, edge_type_ij, k: int, exc
     ranking except inside saturated ties (logits the sigmoid maps to the same float, e.g. all
     above ≈36.7 under "main"), where the reference's own order is whatever numpy's unstable
     argsort leaves — unspecified."""
-    if sigmoid not in SIGMOID_MODES:
-        raise ValueError(f"sigmoid must be one of {list(SIGMOID_MODES)}")
-    i, j = edge_type_ij
     model = opt._model()
-    if (i, j) not in model.edge_type2decoder:
-        raise ValueError(f"unknown edge type {(i, j)}")
-    dec = model.edge_type2decoder[i, j]
+    _edge_type_decoder(model, edge_type_ij, sigmoid)
     fd = dict(feed_dict)
     fd[placeholders["dropout"]] = 0.0
 
     def fn(ctx: RunContext):
-        ets = list(model.edge_types)
-        first = sum(model.edge_types[et] for et in ets[:ets.index((i, j))])  # flat index of relation 0
-        for r in range(first, first + dec.num_types):
-            if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
-                raise ValueError("top_candidates reads the decoder's variables; a latent matrix is fed")
-        row_t, col_t = opt._tables(ctx, i, j)
-        G, l = _stacked_latents(ctx, dec, row_t.shape[1])
-        if G.dim() == 2 and l is None and dec.num_types > 1:  # no per-relation parameter
-            G = G.unsqueeze(0).expand(dec.num_types, -1, -1).contiguous()
+        K, row_t, col_t, G, l = _edge_type_operands("top_candidates", ctx, opt, model, edge_type_ij)
+        if G.dim() == 2 and l is None and K > 1:  # no per-relation parameter
+            G = G.unsqueeze(0).expand(K, -1, -1).contiguous()
         ex = exclude
         if ex is not None and not hasattr(ex, "rowptr"):
             from .sparse import exclusion_csr
@@ -300,26 +319,14 @@ def accuracy_scores_all(sess, opt, placeholders, feed_dict, edges_pos, edges_neg
     (scores [K, 3], (auroc, auprc)).  It is the same entry point with a single segment over the
     already contiguous score arrays, and it is off by default: its cost grows with
     P_total·(P_total + N_total), and it has NOT been measured at the polypharmacy shape."""
-    if sigmoid not in SIGMOID_MODES:
-        raise ValueError(f"sigmoid must be one of {list(SIGMOID_MODES)}")
-    i, j = edge_type_ij
     model = opt._model()
-    if (i, j) not in model.edge_type2decoder:
-        raise ValueError(f"unknown edge type {(i, j)}")
-    dec = model.edge_type2decoder[i, j]
-    K = dec.num_types
+    _edge_type_decoder(model, edge_type_ij, sigmoid)
     fd = dict(feed_dict)
     fd[placeholders["dropout"]] = 0.0
 
     def fn(ctx: RunContext):
-        ets = list(model.edge_types)
-        first = sum(model.edge_types[et] for et in ets[:ets.index((i, j))])  # flat index of relation 0
-        for r in range(first, first + K):
-            if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
-                raise ValueError("accuracy_scores_all reads the decoder's variables; a latent matrix is fed")
-        row_t, col_t = opt._tables(ctx, i, j)
-        G, l = _stacked_latents(ctx, dec, row_t.shape[1])
-        ri, ci, pos_ptr, neg_ptr, rels = pack_edge_samples(edges_pos, edges_neg, (i, j), K,
+        K, row_t, col_t, G, l = _edge_type_operands("accuracy_scores_all", ctx, opt, model, edge_type_ij)
+        ri, ci, pos_ptr, neg_ptr, rels = pack_edge_samples(edges_pos, edges_neg, tuple(edge_type_ij), K,
                                                            (row_t.shape[0], col_t.shape[0]), relations)
         n_seg, P, N = rels.size, int(pos_ptr[-1]), int(neg_ptr[-1])
         # one upload: [row_idx | col_idx | seg_ptr (2·n_seg + 1) | seg_rel (2·n_seg) | neg_ptr | 0, P | 0, N]
@@ -349,14 +356,8 @@ def accuracy_scores_all(sess, opt, placeholders, feed_dict, edges_pos, edges_neg
 def _profile_query(name, sess, opt, placeholders, feed_dict, pairs, edge_type_ij, relations, sigmoid, run):
     """The part pair_profiles and top_relations share: checks, one sess.run at dropout 0 of a Node
     that uploads [row_idx | col_idx | rel_idx] once and returns run(row_t, col_t, ri, ci, G, l, rel_idx)."""
-    if sigmoid not in SIGMOID_MODES:
-        raise ValueError(f"sigmoid must be one of {list(SIGMOID_MODES)}")
-    i, j = edge_type_ij
     model = opt._model()
-    if (i, j) not in model.edge_type2decoder:
-        raise ValueError(f"unknown edge type {(i, j)}")
-    dec = model.edge_type2decoder[i, j]
-    K = dec.num_types
+    K = _edge_type_decoder(model, edge_type_ij, sigmoid).num_types
     pr = np.asarray(pairs, dtype=np.int64)
     if pr.ndim != 2 or pr.shape[1] != 2:
         raise ValueError("pairs must be an [n, 2] array")
@@ -369,15 +370,9 @@ def _profile_query(name, sess, opt, placeholders, feed_dict, pairs, edge_type_ij
     fd[placeholders["dropout"]] = 0.0
 
     def fn(ctx: RunContext):
-        ets = list(model.edge_types)
-        first = sum(model.edge_types[et] for et in ets[:ets.index((i, j))])  # flat index of relation 0
-        for r in range(first, first + K):
-            if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
-                raise ValueError(f"{name} reads the decoder's variables; a latent matrix is fed")
-        row_t, col_t = opt._tables(ctx, i, j)
+        _, row_t, col_t, G, l = _edge_type_operands(name, ctx, opt, model, edge_type_ij)
         if pr.size and (pr.min() < 0 or pr[:, 0].max() >= row_t.shape[0] or pr[:, 1].max() >= col_t.shape[0]):
             raise ValueError("pair outside the embedding tables")
-        G, l = _stacked_latents(ctx, dec, row_t.shape[1])
         n = pr.shape[0]
         host = np.concatenate([pr[:, 0], pr[:, 1], rels]).astype(np.int32)
         buf = torch.from_numpy(host).to(ctx.session.device)

@@ -1121,6 +1121,87 @@ def decoder_score(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: tor
     return out
 
 
+def _check_tensors(pairs, dtype) -> None:
+    """Type, dtype and contiguity of the (tensor, name) pairs; a None tensor is an absent operand."""
+    for t, nm in pairs:
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{nm}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != dtype:
+            raise TypeError(f"{nm}: dtype {t.dtype}, expected {dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{nm}: must be contiguous")
+
+
+def _need_device(pairs) -> None:
+    for t, nm in pairs:
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"{nm}: must be a device (HIP) tensor")
+
+
+WIDTHS_SEG = (range(32, 257, 32), "a multiple of 32, at most 256")  # dg::score_tile's widths
+WIDTHS_MFMA = ((32, 64), "32 or 64")                                # the register-resident tiles'
+
+
+@dataclass(frozen=True)
+class RelOperands:
+    """The per-relation decoder operands of the all-relation entry points (decagon_hip.h,
+    "Per-relation operands"), validated: G [d, d] (shared by every relation) or [K, d, d]; l None
+    (identity), [d] (shared) or [K, d]; K the leading dimension of whichever is per relation,
+    None when nothing is (then any relation index serves)."""
+    tabs: tuple  # (tensor, name) of row_table, col_table, G, l: what the launch reads
+    d: int
+    K: Optional[int]
+    n_rows: int
+    n_cols: int
+
+    @classmethod
+    def build(cls, name, row_table, col_table, G, l, widths, idx=(), empty="empty table") -> "RelOperands":
+        """Checks, in order: type, dtype and contiguity of the operands and of the int32 index
+        tensors `idx` ((tensor, name) pairs); ranks; d; the width rule `widths`; empty tables;
+        the relation counts of G and l agreeing; K >= 1.  Nothing is required on the device yet
+        (_need_device comes last in every wrapper)."""
+        tabs = ((row_table, "row_table"), (col_table, "col_table"), (G, "G"), (l, "l"))
+        _check_tensors(tabs, torch.float32)
+        _check_tensors(idx, torch.int32)
+        if row_table.dim() != 2 or col_table.dim() != 2 or G.dim() not in (2, 3):
+            raise ValueError(f"{name}: tables must be [N, d] and G [d, d] or [K, d, d]")
+        d = G.shape[-1]
+        if G.shape[-2] != d or row_table.shape[1] != d or col_table.shape[1] != d:
+            raise ValueError(f"{name}: d mismatch")
+        if l is not None and (l.dim() not in (1, 2) or l.shape[-1] != d):
+            raise ValueError(f"{name}: d mismatch (l must be [d] or [K, d])")
+        if d not in widths[0]:
+            raise ValueError(f"{name}: d = {d} unsupported ({widths[1]})")
+        n_rows, n_cols = row_table.shape[0], col_table.shape[0]
+        if n_rows < 1 or n_cols < 1:
+            raise ValueError(f"{name}: {empty}")
+        ks = {int(t.shape[0]) for t, per in ((G, G.dim() == 3), (l, l is not None and l.dim() == 2)) if per}
+        if len(ks) > 1:
+            raise ValueError(f"{name}: relation counts disagree: {sorted(ks)}")
+        K = ks.pop() if ks else None
+        if K is not None and K < 1:
+            raise ValueError(f"{name}: no relations")
+        return cls(tabs, d, K, n_rows, n_cols)
+
+    def c_args(self):
+        """(G, g_stride, l, l_stride) as the entry points take them."""
+        G, l = self.tabs[2][0], self.tabs[3][0]
+        return (G.data_ptr(), self.d * self.d if G.dim() == 3 else 0, l.data_ptr() if l is not None else None,
+                self.d if (l is not None and l.dim() == 2) else 0)
+
+    def n_rel(self, n_slots: int, mapped: bool) -> int:
+        """The relation count of the call: K; with nothing per relation, unbounded under a map and
+        the slot count without one (slot s is relation s)."""
+        return self.K if self.K is not None else (2**31 - 1 if mapped else n_slots)
+
+    def need_slots(self, name, n_slots: int, what: str) -> None:
+        """Without a map, per-relation operands bound the slot count."""
+        if self.K is not None and n_slots > self.K:
+            raise ValueError(f"{name}: {n_slots} {what} but {self.K} relations (pass seg_rel)")
+
+
 def decoder_score_seg(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: torch.Tensor,
                       col_idx: torch.Tensor, seg_ptr: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor],
                       seg_rel: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
@@ -1136,29 +1217,8 @@ def decoder_score_seg(row_table: torch.Tensor, col_table: torch.Tensor, row_idx:
     K is the leading dimension of whichever is per relation.  seg_rel: device int32 [n_seg] with
     values in [0, K).  A pair outside the tables, or a segment whose relation is outside [0, K),
     scores NaN."""
-    tabs = [(row_table, "row_table"), (col_table, "col_table"), (G, "G")] + ([(l, "l")] if l is not None else [])
-    idx = [(row_idx, "row_idx"), (col_idx, "col_idx"), (seg_ptr, "seg_ptr")] + (
-        [(seg_rel, "seg_rel")] if seg_rel is not None else [])
-    for ts, dt in ((tabs, torch.float32), (idx, torch.int32)):
-        for t, nm in ts:
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{nm}: expected a torch.Tensor, got {type(t).__name__}")
-            if t.dtype != dt:
-                raise TypeError(f"{nm}: dtype {t.dtype}, expected {dt}")
-            if not t.is_contiguous():
-                raise ValueError(f"{nm}: must be contiguous")
-    if row_table.dim() != 2 or col_table.dim() != 2 or G.dim() not in (2, 3):
-        raise ValueError("decoder_score_seg: tables must be [N, d] and G [d, d] or [K, d, d]")
-    d = G.shape[-1]
-    if G.shape[-2] != d or row_table.shape[1] != d or col_table.shape[1] != d:
-        raise ValueError("decoder_score_seg: d mismatch")
-    if l is not None and (l.dim() not in (1, 2) or l.shape[-1] != d):
-        raise ValueError("decoder_score_seg: d mismatch (l must be [d] or [K, d])")
-    if d < 32 or d % 32 or d > 256:
-        raise ValueError(f"decoder_score_seg: d = {d} unsupported (a multiple of 32, at most 256)")
-    n_rows, n_cols = row_table.shape[0], col_table.shape[0]
-    if n_rows < 1 or n_cols < 1:
-        raise ValueError("decoder_score_seg: empty table")
+    idx = [(row_idx, "row_idx"), (col_idx, "col_idx"), (seg_ptr, "seg_ptr"), (seg_rel, "seg_rel")]
+    ops = RelOperands.build("decoder_score_seg", row_table, col_table, G, l, WIDTHS_SEG, idx)
     n = row_idx.numel()
     if col_idx.numel() != n:
         raise ValueError("decoder_score_seg: row_idx / col_idx length mismatch")
@@ -1167,31 +1227,23 @@ def decoder_score_seg(row_table: torch.Tensor, col_table: torch.Tensor, row_idx:
         raise ValueError("decoder_score_seg: seg_ptr must have n_seg + 1 >= 2 entries")
     if seg_rel is not None and seg_rel.numel() != n_seg:
         raise ValueError("decoder_score_seg: seg_rel must have one entry per segment")
-    ks = {int(t.shape[0]) for t, per in ((G, G.dim() == 3), (l, l is not None and l.dim() == 2)) if per}
-    if len(ks) > 1:
-        raise ValueError(f"decoder_score_seg: relation counts disagree: {sorted(ks)}")
-    K = ks.pop() if ks else None  # None: no per-relation operand, any relation index serves
-    if K is not None and K < 1:
-        raise ValueError("decoder_score_seg: no relations")
-    if K is not None and seg_rel is None and n_seg > K:
-        raise ValueError(f"decoder_score_seg: {n_seg} segments but {K} relations (pass seg_rel)")
+    if seg_rel is None:
+        ops.need_slots("decoder_score_seg", n_seg, "segments")
     if out is not None:
         if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or not out.is_contiguous():
             raise TypeError("out: expected a contiguous float32 torch.Tensor")
         if out.numel() != n:
             raise ValueError("decoder_score_seg: out must have one entry per pair")
-    for t, nm in tabs + idx + ([(out, "out")] if out is not None else []):
-        if not t.is_cuda:
-            raise ValueError(f"{nm}: must be a device (HIP) tensor")
+    _need_device(list(ops.tabs) + idx + [(out, "out")])
     if out is None:
         out = torch.empty(n, device=G.device, dtype=torch.float32)
-    n_rel = K if K is not None else (2**31 - 1 if seg_rel is not None else n_seg)
+    d = ops.d
     fn = _lib.load().dg_decoder_score_seg_f32
-    check(fn(row_table.data_ptr(), d, n_rows, col_table.data_ptr(), d, n_cols, row_idx.data_ptr() if n else None,
-             col_idx.data_ptr() if n else None, seg_ptr.data_ptr(), seg_rel.data_ptr() if seg_rel is not None else None,
-             n_seg, n, G.data_ptr(), d * d if G.dim() == 3 else 0, l.data_ptr() if l is not None else None,
-             d if (l is not None and l.dim() == 2) else 0, n_rel, d, out.data_ptr() if n else None,
-             _stream_ptr(stream)), "dg_decoder_score_seg_f32")
+    check(fn(row_table.data_ptr(), d, ops.n_rows, col_table.data_ptr(), d, ops.n_cols,
+             row_idx.data_ptr() if n else None, col_idx.data_ptr() if n else None, seg_ptr.data_ptr(),
+             seg_rel.data_ptr() if seg_rel is not None else None, n_seg, n, *ops.c_args(),
+             ops.n_rel(n_seg, seg_rel is not None), d, out.data_ptr() if n else None, _stream_ptr(stream)),
+          "dg_decoder_score_seg_f32")
     return out
 
 
@@ -1208,32 +1260,17 @@ def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tens
     exclude: None, a sparse.ExclusionCSR (uploaded here), or a (rowptr, col) pair of device int32
     tensors in that layout (columns ascending and unique within each row).
     upper: only r < c (square tables); no_diag: drop r == c."""
-    tabs = [(row_table, "row_table"), (col_table, "col_table"), (G, "G")] + ([(l, "l")] if l is not None else [])
-    for t, nm in tabs:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{nm}: expected a torch.Tensor, got {type(t).__name__}")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{nm}: dtype {t.dtype}, expected {torch.float32}")
-        if not t.is_contiguous():
-            raise ValueError(f"{nm}: must be contiguous")
-    if row_table.dim() != 2 or col_table.dim() != 2 or G.dim() not in (2, 3):
-        raise ValueError("decoder_topk: tables must be [N, d] and G [d, d] or [K, d, d]")
-    d = G.shape[-1]
-    if G.shape[-2] != d or row_table.shape[1] != d or col_table.shape[1] != d:
-        raise ValueError("decoder_topk: d mismatch")
-    if l is not None and (l.dim() not in (1, 2) or l.shape[-1] != d):
-        raise ValueError("decoder_topk: d mismatch (l must be [d] or [K, d])")
-    if d not in (32, 64):
-        raise ValueError(f"decoder_topk: d = {d} unsupported (32 or 64)")
+    ops = RelOperands.build("decoder_topk", row_table, col_table, G, l, WIDTHS_MFMA,
+                            empty="needs 1 <= N_i·N_j < 2^32")
+    d, n_rows, n_cols = ops.d, ops.n_rows, ops.n_cols
     topk = int(topk)
     if not 1 <= topk <= _lib.DG_TOPK_MAX_K:
         raise ValueError(f"decoder_topk: topk must be in [1, {_lib.DG_TOPK_MAX_K}]")
-    n_rows, n_cols = row_table.shape[0], col_table.shape[0]
-    if n_rows < 1 or n_cols < 1 or n_rows * n_cols >= 2**32:
+    if n_rows * n_cols >= 2**32:
         raise ValueError("decoder_topk: needs 1 <= N_i·N_j < 2^32")
     if upper and n_rows != n_cols:
         raise ValueError("decoder_topk: upper needs square tables")
-    ks = {int(t.shape[0]) for t, per in ((G, G.dim() == 3), (l, l is not None and l.dim() == 2)) if per}
+    ks = set() if ops.K is None else {ops.K}  # … and the exclusion's relation count
     ex_rowptr = ex_col = None
     if exclude is not None:
         if hasattr(exclude, "rowptr") and hasattr(exclude, "n_rels"):
@@ -1251,9 +1288,7 @@ def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tens
     K = ks.pop() if ks else 1
     if K < 1:
         raise ValueError("decoder_topk: no relations")
-    for t, nm in tabs:
-        if not t.is_cuda:
-            raise ValueError(f"{nm}: must be a device (HIP) tensor")
+    _need_device(ops.tabs)
     dev = G.device
     if isinstance(ex_rowptr, np.ndarray):
         ex_rowptr, ex_col = torch.from_numpy(ex_rowptr).to(dev), torch.from_numpy(ex_col).to(dev)
@@ -1273,9 +1308,7 @@ def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tens
     counts = torch.empty(K, dtype=torch.int32, device=dev)
     flags = (_lib.DG_TOPK_UPPER if upper else 0) | (_lib.DG_TOPK_NO_DIAG if no_diag else 0)
     check(lib.dg_decoder_topk_f32(
-        row_table.data_ptr(), d, n_rows, col_table.data_ptr(), d, n_cols, G.data_ptr(),
-        d * d if G.dim() == 3 else 0, l.data_ptr() if l is not None else None,
-        d if (l is not None and l.dim() == 2) else 0, K, d, topk,
+        row_table.data_ptr(), d, n_rows, col_table.data_ptr(), d, n_cols, *ops.c_args(), K, d, topk,
         ex_rowptr.data_ptr() if ex_rowptr is not None else None,
         ex_col.data_ptr() if ex_col is not None else None, flags, scores.data_ptr(), rows.data_ptr(),
         cols.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream_ptr(stream)),
@@ -1290,64 +1323,28 @@ def cross_slot_chunk(n_pairs: int, n_sel: int) -> int:
 
 
 def _cross_operands(name, row_table, col_table, row_idx, col_idx, G, l, rel_idx):
-    """Validation shared by decoder_score_cross and decoder_top_relations, in decoder_score_seg's
-    order (type, dtype, contiguity, shapes): (d, n_rows, n_cols, n_pairs, n_sel, n_rel)."""
-    tabs = [(row_table, "row_table"), (col_table, "col_table"), (G, "G")] + ([(l, "l")] if l is not None else [])
-    idx = [(row_idx, "row_idx"), (col_idx, "col_idx")] + ([(rel_idx, "rel_idx")] if rel_idx is not None else [])
-    for ts, dt in ((tabs, torch.float32), (idx, torch.int32)):
-        for t, nm in ts:
-            if not isinstance(t, torch.Tensor):
-                raise TypeError(f"{nm}: expected a torch.Tensor, got {type(t).__name__}")
-            if t.dtype != dt:
-                raise TypeError(f"{nm}: dtype {t.dtype}, expected {dt}")
-            if not t.is_contiguous():
-                raise ValueError(f"{nm}: must be contiguous")
-    if row_table.dim() != 2 or col_table.dim() != 2 or G.dim() not in (2, 3):
-        raise ValueError(f"{name}: tables must be [N, d] and G [d, d] or [K, d, d]")
-    d = G.shape[-1]
-    if G.shape[-2] != d or row_table.shape[1] != d or col_table.shape[1] != d:
-        raise ValueError(f"{name}: d mismatch")
-    if l is not None and (l.dim() not in (1, 2) or l.shape[-1] != d):
-        raise ValueError(f"{name}: d mismatch (l must be [d] or [K, d])")
-    if d not in (32, 64):
-        raise ValueError(f"{name}: d = {d} unsupported (32 or 64)")
-    n_rows, n_cols = row_table.shape[0], col_table.shape[0]
-    if n_rows < 1 or n_cols < 1:
-        raise ValueError(f"{name}: empty table")
+    """Validation shared by decoder_score_cross and decoder_top_relations: (ops, n_pairs, n_sel)."""
+    ops = RelOperands.build(name, row_table, col_table, G, l, WIDTHS_MFMA,
+                            [(row_idx, "row_idx"), (col_idx, "col_idx"), (rel_idx, "rel_idx")])
     if row_idx.dim() != 1 or col_idx.dim() != 1 or col_idx.numel() != row_idx.numel():
         raise ValueError(f"{name}: row_idx / col_idx must be vectors of one length")
     if rel_idx is not None and (rel_idx.dim() != 1 or rel_idx.numel() < 1):
         raise ValueError(f"{name}: rel_idx must be a non-empty vector")
-    ks = {int(t.shape[0]) for t, per in ((G, G.dim() == 3), (l, l is not None and l.dim() == 2)) if per}
-    if len(ks) > 1:
-        raise ValueError(f"{name}: relation counts disagree: {sorted(ks)}")
-    K = ks.pop() if ks else None  # None: no per-relation operand, any relation index serves
-    if K is not None and K < 1:
-        raise ValueError(f"{name}: no relations")
-    if rel_idx is None and K is None:
+    if rel_idx is None and ops.K is None:
         raise ValueError(f"{name}: no per-relation operand: pass rel_idx to name the slots")
-    n_sel = rel_idx.numel() if rel_idx is not None else K
-    n_rel = K if K is not None else 2**31 - 1
-    return d, n_rows, n_cols, row_idx.numel(), n_sel, n_rel
+    return ops, row_idx.numel(), rel_idx.numel() if rel_idx is not None else ops.K
 
 
-def _need_device(pairs) -> None:
-    for t, nm in pairs:
-        if t is not None and not t.is_cuda:
-            raise ValueError(f"{nm}: must be a device (HIP) tensor")
-
-
-def _score_cross_call(row_table, col_table, row_idx, col_idx, G, l, rel_idx, dims, p0, n, out, stream) -> None:
+def _score_cross_call(ops, row_idx, col_idx, rel_idx, n_sel, p0, n, out, stream) -> None:
     """Pairs [p0, p0 + n) into the rows of `out` (row stride out.stride(0)); arguments validated."""
-    d, n_rows, n_cols, _, n_sel, n_rel = dims
     if n == 0:
         return
+    (row_table, _), (col_table, _) = ops.tabs[:2]
     check(_lib.load().dg_decoder_score_cross_f32(
-        row_table.data_ptr(), d, n_rows, col_table.data_ptr(), d, n_cols, row_idx.data_ptr() + 4 * p0,
-        col_idx.data_ptr() + 4 * p0, n, G.data_ptr(), d * d if G.dim() == 3 else 0,
-        l.data_ptr() if l is not None else None, d if (l is not None and l.dim() == 2) else 0,
-        rel_idx.data_ptr() if rel_idx is not None else None, n_sel, n_rel, d, out.data_ptr(), out.stride(0),
-        _stream_ptr(stream)), "dg_decoder_score_cross_f32")
+        row_table.data_ptr(), ops.d, ops.n_rows, col_table.data_ptr(), ops.d, ops.n_cols,
+        row_idx.data_ptr() + 4 * p0, col_idx.data_ptr() + 4 * p0, n, *ops.c_args(),
+        rel_idx.data_ptr() if rel_idx is not None else None, n_sel, ops.n_rel(n_sel, rel_idx is not None), ops.d,
+        out.data_ptr(), out.stride(0), _stream_ptr(stream)), "dg_decoder_score_cross_f32")
 
 
 def decoder_score_cross(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: torch.Tensor,
@@ -1367,8 +1364,7 @@ def decoder_score_cross(row_table: torch.Tensor, col_table: torch.Tensor, row_id
     stride(0) ≥ n_sel); its columns past n_sel are not written, and out[:, :n_sel] is returned.
     A pair outside the tables scores a row of NaN, a slot whose relation is outside [0, K) a
     column of NaN."""
-    dims = _cross_operands("decoder_score_cross", row_table, col_table, row_idx, col_idx, G, l, rel_idx)
-    n, n_sel = dims[3], dims[4]
+    ops, n, n_sel = _cross_operands("decoder_score_cross", row_table, col_table, row_idx, col_idx, G, l, rel_idx)
     if out is not None:
         if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
             raise TypeError("out: expected a float32 torch.Tensor")
@@ -1376,13 +1372,12 @@ def decoder_score_cross(row_table: torch.Tensor, col_table: torch.Tensor, row_id
             raise ValueError("decoder_score_cross: out must be [P, >= n_sel]")
         if out.stride(1) != 1 or out.stride(0) < max(n_sel, out.shape[1]):
             raise ValueError("decoder_score_cross: out must have stride(1) == 1 and stride(0) >= n_sel")
-    _need_device([(row_table, "row_table"), (col_table, "col_table"), (G, "G"), (l, "l"), (row_idx, "row_idx"),
-                  (col_idx, "col_idx"), (rel_idx, "rel_idx"), (out, "out")])
+    _need_device(list(ops.tabs) + [(row_idx, "row_idx"), (col_idx, "col_idx"), (rel_idx, "rel_idx"), (out, "out")])
     if n * (out.stride(0) if out is not None else n_sel) >= 2**38:
         raise ValueError("decoder_score_cross: P·ld_out must stay below 2^38 (score in chunks of pairs)")
     if out is None:
         out = torch.empty((n, n_sel), device=G.device, dtype=torch.float32)
-    _score_cross_call(row_table, col_table, row_idx, col_idx, G, l, rel_idx, dims, 0, n, out, stream)
+    _score_cross_call(ops, row_idx, col_idx, rel_idx, n_sel, 0, n, out, stream)
     return out[:, :n_sel]
 
 
@@ -1447,13 +1442,11 @@ def decoder_top_relations(row_table: torch.Tensor, col_table: torch.Tensor, row_
     outputs, so no P×n_sel matrix exists at any time.  A pair's scores do not depend on its
     neighbours and the selection order is total: the result is the same, bytes and all, whatever
     the bound."""
-    dims = _cross_operands("decoder_top_relations", row_table, col_table, row_idx, col_idx, G, l, rel_idx)
-    n, n_sel = dims[3], dims[4]
+    ops, n, n_sel = _cross_operands("decoder_top_relations", row_table, col_table, row_idx, col_idx, G, l, rel_idx)
     topk = int(topk)
     if not 1 <= topk <= _lib.DG_TOPK_MAX_K:
         raise ValueError(f"decoder_top_relations: topk must be in [1, {_lib.DG_TOPK_MAX_K}]")
-    _need_device([(row_table, "row_table"), (col_table, "col_table"), (G, "G"), (l, "l"), (row_idx, "row_idx"),
-                  (col_idx, "col_idx"), (rel_idx, "rel_idx")])
+    _need_device(list(ops.tabs) + [(row_idx, "row_idx"), (col_idx, "col_idx"), (rel_idx, "rel_idx")])
     dev = G.device
     vals = torch.empty((n, topk), dtype=torch.float32, device=dev)
     idx = torch.empty((n, topk), dtype=torch.int32, device=dev)
@@ -1463,7 +1456,7 @@ def decoder_top_relations(row_table: torch.Tensor, col_table: torch.Tensor, row_
         ws = torch.empty((chunks[0][1] - chunks[0][0], n_sel), dtype=torch.float32, device=dev)
     for p0, p1 in chunks:
         m = p1 - p0
-        _score_cross_call(row_table, col_table, row_idx, col_idx, G, l, rel_idx, dims, p0, m, ws, stream)
+        _score_cross_call(ops, row_idx, col_idx, rel_idx, n_sel, p0, m, ws, stream)
         _row_topk_call(ws[:m], topk, vals[p0:p1], idx[p0:p1], counts[p0:p1], stream)
     return vals, idx, counts
 
@@ -1922,26 +1915,11 @@ class PreparedDecoderGradSeg:
     def __init__(self, row_table, col_table, rows, cols, neg_rows, seg_ptr, seg_rel, pos, neg, G, l,
                  margin: float, dG: Optional[torch.Tensor] = None, dl: Optional[torch.Tensor] = None,
                  dG_diag: Optional[torch.Tensor] = None):
-        for t, nm, dt in ((row_table, "row_table", torch.float32), (col_table, "col_table", torch.float32),
-                          (rows, "rows", torch.int32), (cols, "cols", torch.int32),
-                          (neg_rows, "neg_rows", torch.int32), (seg_ptr, "seg_ptr", torch.int32),
-                          (pos, "pos", torch.float32), (neg, "neg", torch.float32), (G, "G", torch.float32)):
-            _dev(t, dt, nm)
-        if seg_rel is not None:
-            _dev(seg_rel, torch.int32, "seg_rel")
-        if l is not None:
-            _dev(l, torch.float32, "l")
-        if row_table.dim() != 2 or col_table.dim() != 2 or G.dim() not in (2, 3):
-            raise ValueError("decoder_grad_seg: tables must be [N, d] and G [d, d] or [K, d, d]")
-        d = G.shape[-1]
-        if d not in (32, 64):
-            raise ValueError(f"decoder_grad_seg: d = {d} unsupported (32 or 64)")
-        if G.shape[-2] != d or row_table.shape[1] != d or col_table.shape[1] != d:
-            raise ValueError("decoder_grad_seg: d mismatch")
-        if l is not None and (l.dim() not in (1, 2) or l.shape[-1] != d):
-            raise ValueError("decoder_grad_seg: d mismatch (l must be [d] or [K, d])")
-        if row_table.shape[0] < 1 or col_table.shape[0] < 1:
-            raise ValueError("decoder_grad_seg: empty table")
+        idx = [(rows, "rows"), (cols, "cols"), (neg_rows, "neg_rows"), (seg_ptr, "seg_ptr"), (seg_rel, "seg_rel")]
+        outs = [(pos, "pos"), (neg, "neg"), (dG, "dG"), (dl, "dl"), (dG_diag, "dG_diag")]
+        ops = RelOperands.build("decoder_grad_seg", row_table, col_table, G, l, WIDTHS_MFMA, idx)
+        _check_tensors(outs, torch.float32)
+        d, K = ops.d, ops.K
         n = rows.numel()
         if any(t.numel() != n for t in (cols, neg_rows, pos, neg)):
             raise ValueError("decoder_grad_seg: batch sizes differ")
@@ -1951,12 +1929,8 @@ class PreparedDecoderGradSeg:
         if seg_rel is not None and seg_rel.numel() != n_seg:
             raise ValueError("decoder_grad_seg: seg_rel must have one entry per segment")
         g_per, l_per = G.dim() == 3, l is not None and l.dim() == 2
-        ks = {int(t.shape[0]) for t, per in ((G, g_per), (l, l_per)) if per}
-        if len(ks) > 1:
-            raise ValueError(f"decoder_grad_seg: relation counts disagree: {sorted(ks)}")
-        K = ks.pop() if ks else None
-        if K is not None and seg_rel is None and n_seg > K:
-            raise ValueError(f"decoder_grad_seg: {n_seg} segments but {K} relations (pass seg_rel)")
+        if seg_rel is None:
+            ops.need_slots("decoder_grad_seg", n_seg, "segments")
         if dl is not None and not l_per:
             raise ValueError("dl needs a per-relation diagonal l [K, d]")
         if dG_diag is not None and not g_per:
@@ -1964,10 +1938,9 @@ class PreparedDecoderGradSeg:
         n_out = K if K is not None else n_seg
         for t, nm, sz in ((dG, "dG", (n_out if g_per else 1) * d * d), (dl, "dl", n_out * d),
                           (dG_diag, "dG_diag", n_out * d)):
-            if t is not None:
-                _dev(t, torch.float32, nm)
-                if t.numel() != sz:
-                    raise ValueError(f"{nm} must have {sz} elements")
+            if t is not None and t.numel() != sz:
+                raise ValueError(f"{nm} must have {sz} elements")
+        _need_device(list(ops.tabs) + idx + outs)
         dev = G.device
         self.mv = torch.empty((n, d), device=dev)
         self.grad_cols = torch.empty((n, d), device=dev)
@@ -1977,11 +1950,10 @@ class PreparedDecoderGradSeg:
         self._ws = torch.empty(max(1, nbytes // 4), device=dev) if vars_ else None
         self._keep = (row_table, col_table, rows, cols, neg_rows, seg_ptr, seg_rel, pos, neg, G, l, dG, dl, dG_diag)
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        n_rel = K if K is not None else (2**31 - 1 if seg_rel is not None else n_seg)
-        self._args = [row_table.data_ptr(), d, row_table.shape[0], col_table.data_ptr(), d, col_table.shape[0],
+        self._args = [row_table.data_ptr(), d, ops.n_rows, col_table.data_ptr(), d, ops.n_cols,
                       ptr(rows) if n else None, ptr(cols) if n else None, ptr(neg_rows) if n else None,
                       seg_ptr.data_ptr(), ptr(seg_rel), n_seg, n, ptr(pos) if n else None, ptr(neg) if n else None,
-                      float(margin), G.data_ptr(), d * d if g_per else 0, ptr(l), d if l_per else 0, n_rel, d,
+                      float(margin), *ops.c_args(), ops.n_rel(n_seg, seg_rel is not None), d,
                       ptr(self.mv) if n else None, ptr(self.grad_cols) if n else None, ptr(dG), ptr(dl),
                       ptr(dG_diag), ptr(self._ws), nbytes if vars_ else 0]
         self._fn = lib.dg_decoder_grad_seg_f32

@@ -29,7 +29,7 @@ import torch
 
 from . import kernels
 from .epochs import DeviceBatches, _items
-from .evaluate import _stacked_latents
+from .evaluate import _stacked_latents, first_relation
 from .graph import InvalidArgumentError, Node, RunContext
 
 EdgeType = Tuple[int, int]
@@ -168,9 +168,8 @@ def _decoder_meta(ctx: RunContext, opt, model, et: EdgeType) -> dict:
     dec = model.edge_type2decoder[et]
     meta = cache.get(key)
     if meta is None or meta["flat_ptr"] != dec.flat.data_ptr():
-        ets = list(model.edge_types)
         K = model.edge_types[et]
-        first = sum(model.edge_types[t] for t in ets[:ets.index(et)])
+        first = first_relation(model, et)
         specs = [dec.latent(k) for k in range(K)]
         gk, lk = specs[0][0], specs[0][2]
         off = lambda c: (specs[0][c].tensor.data_ptr() - dec.flat.data_ptr()) // 4  # noqa: E731
@@ -238,7 +237,6 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
         negs_host = None
     else:
         negs_host = _negatives(neg_samples, packed, shapes)
-    ets = list(model.edge_types)
 
     def fn(ctx: RunContext):
         if not ctx.training:
@@ -253,7 +251,7 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
                 if any(nd in lat for nd in ctx.feeds):
                     raise InvalidArgumentError("train_step_all trains the decoder's variables; a latent matrix is fed")
                 continue
-            first = sum(model.edge_types[t] for t in ets[:ets.index(et)])
+            first = first_relation(model, et)
             for r in range(first, first + model.edge_types[et]):
                 if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
                     raise InvalidArgumentError("train_step_all trains the decoder's variables; a latent matrix is fed")
@@ -296,7 +294,7 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
                     negs = buf[2 * n:3 * n]
             t0 = _stage("operands", t0)
             if not fed:
-                first = meta["first"] if tb is not None else sum(model.edge_types[t] for t in ets[:ets.index(et)])
+                first = meta["first"] if tb is not None else first_relation(model, et)
                 s = opt._sampler(ctx)
                 stack = _alias_stack(ctx, opt, et, first, K)
                 if stack.shape[1] > row_t.shape[0]:

@@ -909,6 +909,22 @@ int dg_rank_metrics_ex_f32(const float* pos, int32_t n_pos, const float* neg, in
                            int32_t mode, double* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------
+ * Per-relation operands: what (G, g_stride, l, l_stride, n_rel) and a relation map mean to the
+ * entry points that take every relation of one edge type in one pass (dg_decoder_topk_f32,
+ * dg_decoder_score_seg_f32, dg_decoder_score_cross_f32, dg_decoder_grad_seg_f32).
+ *   G_k = G + k*g_stride, row-major d x d: g_stride 0 (one G shared by every relation: DEDICOM's
+ *         R) or d*d (per relation: Bilinear);
+ *   l_k = l + k*l_stride: l_stride 0 (shared) or d (per relation); l NULL = identity, and then
+ *         l_stride is ignored.  Any other stride is DG_EINVAL.
+ * A SLOT of a call (a segment, a selected column, a relation of the grid) is relation k = map[s]
+ * (the call's seg_rel / rel_idx, device int32, never read on the host), or k = s where the map is
+ * NULL or the call has none.  With a map, n_rel >= 1 bounds its values: a slot whose relation lies
+ * outside [0, n_rel) reads no operand and scores NaN (the backward skips it).  Without a map every
+ * slot is in range, and a per-relation operand needs slots <= n_rel (DG_EINVAL otherwise); where
+ * no operand is per relation, any relation index serves.
+ * -------------------------------------------------------------------------------------- */
+
+/* --------------------------------------------------------------------------------------
  * Top-k candidate ranking (ABI 39): for every relation k < n_rel of one edge type, the `topk`
  * highest-scoring permitted pairs (r, c), r < n_rows, c < n_cols, of
  *
@@ -920,9 +936,8 @@ int dg_rank_metrics_ex_f32(const float* pos, int32_t n_pos, const float* neg, in
  *           main/Predictor/NpPredictor.py:293-313.
  *
  * Operands: row_table / col_table: row r at table + r*ld (ld >= d, ld % 4 == 0, 16-byte aligned);
- * G_k = G + k*g_stride, g_stride 0 (one shared d x d G: DEDICOM's R) or d*d (per relation:
- * Bilinear), row-major; l_k = l + k*l_stride, l_stride 0 (shared) or d (per relation), l NULL =
- * identity.  d is 32 or 64; 1 <= topk <= DG_TOPK_MAX_K; n_rows * n_cols < 2^32.
+ * G_k, l_k: "Per-relation operands" above (no map: the grid's relation k is relation k).
+ * d is 32 or 64; 1 <= topk <= DG_TOPK_MAX_K; n_rows * n_cols < 2^32.
  *
  * Permitted: (r, c) is not in relation k's exclusion set; with DG_TOPK_UPPER only r < c (needs
  * n_rows == n_cols); with DG_TOPK_NO_DIAG not r == c.  The exclusion sets are a relation-stacked
@@ -971,10 +986,8 @@ int dg_decoder_topk_f32(const float* row_table, int64_t ld_row, int32_t n_rows, 
  *
  *     out[p] = (row_table[row_idx[p]] ∘ l_k)ᵀ · G_k · (l_k ∘ col_table[col_idx[p]])
  *
- * with the operand conventions of dg_decoder_topk_f32 (G_k = G + k*g_stride, g_stride 0 or d*d;
- * l_k = l + k*l_stride, l_stride 0 or d; l NULL = identity) and d as dg_decoder_score_f32
- * (d % 32 == 0, d <= 256).  0 <= k < n_rel; without seg_rel, per-relation operands need
- * n_seg <= n_rel.  n_pairs + 32*n_seg < 2^31.  One wave scores one 32-pair tile of one segment
+ * with G_k, l_k, n_rel as "Per-relation operands" above (the slots are the segments) and d as
+ * dg_decoder_score_f32 (d % 32 == 0, d <= 256).  n_pairs + 32*n_seg < 2^31.  One wave scores one 32-pair tile of one segment
  * with the tile routine of dg_decoder_score_f32, so a segment's scores equal that entry point's
  * on the segment's pairs with G_k, l_k bit for bit.  A pair whose index lies outside
  * [0, n_rows) x [0, n_cols), and every pair of a segment whose relation lies outside [0, n_rel),
@@ -1018,8 +1031,7 @@ int32_t dg_seg_tile_lookup(const int32_t* seg_ptr, int32_t n_seg, int32_t tile, 
  *
  *     out[p*ld_out + s] = (row_table[row_idx[p]] ∘ l_k)ᵀ · G_k · (l_k ∘ col_table[col_idx[p]])
  *
- * with the operand conventions of dg_decoder_topk_f32 and dg_decoder_score_seg_f32 (G_k = G +
- * k*g_stride, g_stride 0 or d*d; l_k = l + k*l_stride, l_stride 0 or d; l NULL = identity) and d
+ * with G_k, l_k, n_rel as "Per-relation operands" above (the slots are the n_sel columns) and d
  * 32 or 64.  rel_idx may repeat relations, in any order.  ld_out >= n_sel; columns
  * [n_sel, ld_out) of a row are not written.  Every out[p, s] equals, bit for bit, what
  * dg_decoder_score_f32 returns for that pair with G_k, l_k, whatever the pair's place in the
@@ -1074,8 +1086,8 @@ int dg_row_topk_f32(const float* x, int64_t ld, int32_t n_rows, int32_t n_cols, 
  * dg_decoder_grad_seg_f32: dg_decoder_grad_f32 over packed SEGMENTS with the conventions of
  * dg_decoder_score_seg_f32: segment s is pairs [seg_ptr[s], seg_ptr[s+1]) (seg_ptr int32
  * [n_seg + 1] on the device, never read on the host; segments may be empty) and belongs to
- * relation k = seg_rel[s] (seg_rel NULL: k = s), G_k = G + k*g_stride (g_stride 0 or d*d),
- * l_k = l + k*l_stride (l_stride 0 or d; l NULL = identity), 0 <= k < n_rel.  The relations in
+ * relation k = seg_rel[s] (seg_rel NULL: k = s), with G_k, l_k, n_rel as "Per-relation operands"
+ * above.  The relations in
  * seg_rel must be DISTINCT (two segments of one relation would both write its outputs).
  * d is 32 or 64 (the per-segment dM buffer is n_seg*d*d floats).  With M_k = L_k·G_k·L_k, u / un
  * / v the rows row_table[rows[p]] / row_table[neg_rows[p]] / col_table[cols[p]], and

@@ -176,3 +176,55 @@ def test_occurrence_list_against_brute_force():
         seg = list(zip(sign[node_ptr[r]:node_ptr[r + 1]], item[node_ptr[r]:node_ptr[r + 1]]))
         assert seg == sorted(seg), r
     assert np.array_equal(got, want)
+
+
+def test_grad_seg_wrapper_validates_shapes_before_the_device(monkeypatch):
+    """PreparedDecoderGradSeg checks its operands like its four all-relation siblings
+    (kernels.RelOperands): shapes first, with their messages, on host tensors and without the
+    library; the device requirement comes last."""
+    from decagon_amd import _lib, kernels
+
+    def no_library(*a, **k):
+        raise AssertionError("the library was loaded before the arguments were checked")
+
+    monkeypatch.setattr(_lib, "load", no_library)
+    E = torch.zeros(10, 32)
+    G = torch.zeros(32, 32)
+    l = torch.zeros(3, 32)
+    idx = torch.zeros(8, dtype=torch.int32)
+    sc = torch.zeros(8)
+    ptr = torch.tensor([0, 3, 3, 8], dtype=torch.int32)
+
+    def f(row=E, col=E, rows=idx, cols=idx, negs=idx, seg_ptr=ptr, seg_rel=None, pos=sc, neg=sc, G=G, l=l, **kw):
+        return kernels.PreparedDecoderGradSeg(row, col, rows, cols, negs, seg_ptr, seg_rel, pos, neg, G, l, 0.1, **kw)
+
+    with pytest.raises(TypeError, match="dtype"):
+        f(rows=idx.long())
+    with pytest.raises(TypeError, match="dtype"):
+        f(pos=sc.double())
+    with pytest.raises(TypeError, match="torch.Tensor"):
+        f(row=E.numpy())
+    with pytest.raises(ValueError, match="contiguous"):
+        f(row=torch.zeros(10, 64)[:, ::2])
+    with pytest.raises(ValueError, match="d mismatch"):
+        f(row=torch.zeros(10, 64))
+    with pytest.raises(ValueError, match="d mismatch"):
+        f(l=torch.zeros(3, 16))
+    with pytest.raises(ValueError, match="unsupported"):
+        f(row=torch.zeros(10, 16), col=torch.zeros(10, 16), G=torch.zeros(16, 16), l=None)
+    with pytest.raises(ValueError, match="unsupported"):  # (the segmented scorer's widths are not the backward's)
+        f(row=torch.zeros(10, 96), col=torch.zeros(10, 96), G=torch.zeros(96, 96), l=None)
+    with pytest.raises(ValueError, match="disagree"):
+        f(G=torch.zeros(4, 32, 32))
+    with pytest.raises(ValueError, match="pass seg_rel"):
+        f(l=torch.zeros(2, 32))
+    with pytest.raises(ValueError, match="seg_rel"):
+        f(seg_rel=torch.zeros(2, dtype=torch.int32))
+    with pytest.raises(ValueError, match="batch sizes differ"):
+        f(cols=idx[:5])
+    with pytest.raises(ValueError, match="dl needs"):
+        f(l=torch.zeros(32), dl=torch.zeros(3, 32))
+    with pytest.raises(ValueError, match="device"):  # every shape is right: only now the device
+        f()
+    with pytest.raises(ValueError, match="device"):
+        f(seg_rel=torch.zeros(3, dtype=torch.int32), dl=torch.zeros(3, 32))
