@@ -320,6 +320,8 @@ SIGNATURES = {
     "dg_row_topk_workspace": (c_int64, [c_int32, c_int32, c_int32]),
     "dg_row_topk_f32": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_int64, c_void_p]),
+    "dg_row_topk_excl_f32": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "dg_decoder_grad_seg_workspace": (c_int64, [c_int32, c_int32]),
     "dg_decoder_grad_seg_f32": (
         c_int32,

@@ -25,6 +25,9 @@
 // Row top-k.  One wave per row reads the row once, coalesced, through the list of topk_list.h
 // (append above the threshold, sort when full, truncate) under the keys of dg_decoder_topk_f32
 // with the column as the index: the unique top-k of the row whatever the tiling.
+// dg_row_topk_excl_f32 selects among the columns a per-row ascending list does not name (a pair's
+// known relations — what the reference drops on the host after _predictEdges per relation id): a
+// sibling kernel merges the list into the same single pass, row_topk_kernel itself is untouched.
 #include "common.h"
 #include "decoder_tile.h"
 #include "rel_operands.h"
@@ -232,6 +235,87 @@ __global__ __launch_bounds__(64) void row_topk_kernel(const RowTopkArgs a) {
     if (lane == 0) a.out_count[row] = tk.n;
 }
 
+struct RowTopkExclArgs {
+    RowTopkArgs t;
+    const int32_t* excl_ptr;
+    const int32_t* excl_slot;
+    int32_t excl_nnz;
+};
+
+// row_topk_kernel over the columns that the row's ascending list excl_slot[e0, e1) does not name.
+// Columns and list both ascend, so the wave merges them: the lanes hold the next 64 entries of the
+// list in registers (one coalesced load per 64 entries), the entries that fall into the 64-column
+// block at c0 tag position entry − c0 of a 64-entry LDS strip behind the list's buffer with the
+// block's number, and lane i pushes its column only when strip[i] does not carry that number.
+// The cursor then passes the entries below c0 + 64.  The tag makes a strip entry of an earlier
+// block stale by itself, so the strip is cleared once.  Every index is formed from clamped,
+// wave-uniform bounds: cur ≤ win + 64 and cur ≤ e1 ≤ excl_nnz hold whatever the list contains, and
+// the strip is written only at entry − c0 ∈ [0, 64).
+__global__ __launch_bounds__(64) void row_topk_excl_kernel(const RowTopkExclArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char row_topk_excl_smem[];
+    const int lane = threadIdx.x;
+    const int64_t row = blockIdx.x;
+    const float* x = a.t.x + row * a.t.ld;
+    dg::WaveTopK tk;
+    tk.init(reinterpret_cast<uint64_t*>(row_topk_excl_smem), a.t.cap, a.t.topk, lane);
+    int32_t* strip = reinterpret_cast<int32_t*>(row_topk_excl_smem + (size_t)a.t.cap * 8);
+    strip[lane] = 0;  // (block numbers start at 1)
+    dg::wave_lds_sync();
+
+    int cur = __builtin_amdgcn_readfirstlane(a.excl_ptr[row]);
+    int e1 = __builtin_amdgcn_readfirstlane(a.excl_ptr[row + 1]);
+    cur = min(max(cur, 0), a.excl_nnz);
+    e1 = min(max(e1, cur), a.excl_nnz);  // a non-increasing pair: an empty list
+    int win = cur;                       // lane i holds entry win + i, where the list has one
+    int32_t ent = lane < e1 - win ? a.excl_slot[(int64_t)win + lane] : 0;
+#pragma unroll 1
+    for (int c0 = 0; c0 < a.t.n_cols; c0 += dg::kWave) {
+        const int c = c0 + lane;
+        const bool ok = c < a.t.n_cols;
+        const int tag = (c0 >> 6) + 1;
+        bool keep = ok;
+        if (cur < e1) {  // (wave-uniform)
+            const int64_t c_end = (int64_t)c0 + dg::kWave;
+            for (;;) {
+                const bool below = lane >= cur - win && lane < e1 - win && (int64_t)ent < c_end;
+                if (below && ent >= c0) strip[ent - c0] = tag;
+                cur += __popcll(__ballot(below));
+                if (cur - win < dg::kWave || cur >= e1) break;
+                win = cur;  // every held entry lies below the block's end: the next 64
+                ent = lane < e1 - win ? a.excl_slot[(int64_t)win + lane] : 0;
+            }
+            dg::wave_lds_sync();
+            keep = ok && strip[lane] != tag;
+        }
+        tk.push(dg::make_key(ok ? x[c] : 0.f, (uint32_t)c), keep);
+    }
+    tk.compact();
+    for (int t = lane; t < a.t.topk; t += dg::kWave) {
+        const uint64_t key = tk.buf[t];
+        const int64_t o = row * a.t.topk + t;
+        const bool live = t < tk.n;
+        a.t.out_val[o] = live ? dg::key_score(key) : -__builtin_inff();
+        a.t.out_idx[o] = live ? (int32_t)~(uint32_t)key : -1;
+    }
+    if (lane == 0) a.t.out_count[row] = tk.n;
+}
+
+// The argument checks of both row selections, and the launch arguments when there is work.
+int row_topk_args(const float* x, int64_t ld, int32_t n_rows, int32_t n_cols, int32_t topk, float* out_val,
+                  int32_t* out_idx, int32_t* out_count, RowTopkArgs& a) {
+    if (n_rows < 0 || n_cols < 1 || topk < 1 || topk > DG_TOPK_MAX_K || ld < n_cols) return DG_EINVAL;
+    if (n_rows > 0 && (!x || !out_val || !out_idx || !out_count)) return DG_EINVAL;
+    a.x = x;
+    a.out_val = out_val;
+    a.out_idx = out_idx;
+    a.out_count = out_count;
+    a.ld = ld;
+    a.n_cols = n_cols;
+    a.topk = topk;
+    a.cap = dg::list_cap(topk);
+    return DG_OK;
+}
+
 }  // namespace
 
 extern "C" int32_t dg_decoder_score_cross_chunk(int32_t n_pairs, int32_t n_sel) {
@@ -290,19 +374,29 @@ extern "C" int dg_row_topk_f32(const float* x, int64_t ld, int32_t n_rows, int32
                                float* out_val, int32_t* out_idx, int32_t* out_count, void* workspace,
                                int64_t workspace_bytes, void* stream) {
     (void)workspace, (void)workspace_bytes;
-    if (n_rows < 0 || n_cols < 1 || topk < 1 || topk > DG_TOPK_MAX_K || ld < n_cols) return DG_EINVAL;
-    if (n_rows > 0 && (!x || !out_val || !out_idx || !out_count)) return DG_EINVAL;
-    if (n_rows == 0) return DG_OK;
     RowTopkArgs a{};
-    a.x = x;
-    a.out_val = out_val;
-    a.out_idx = out_idx;
-    a.out_count = out_count;
-    a.ld = ld;
-    a.n_cols = n_cols;
-    a.topk = topk;
-    a.cap = dg::list_cap(topk);
+    if (row_topk_args(x, ld, n_rows, n_cols, topk, out_val, out_idx, out_count, a) != DG_OK) return DG_EINVAL;
+    if (n_rows == 0) return DG_OK;
     hipLaunchKernelGGL(row_topk_kernel, dim3((unsigned)n_rows), dim3(64), a.cap * 8,
                        reinterpret_cast<hipStream_t>(stream), a);
+    return dg::launch_status();
+}
+
+extern "C" int dg_row_topk_excl_f32(const float* x, int64_t ld, int32_t n_rows, int32_t n_cols, int32_t topk,
+                                    const int32_t* excl_ptr, const int32_t* excl_slot, int32_t excl_nnz,
+                                    float* out_val, int32_t* out_idx, int32_t* out_count, void* stream) {
+    RowTopkExclArgs a{};
+    if (row_topk_args(x, ld, n_rows, n_cols, topk, out_val, out_idx, out_count, a.t) != DG_OK) return DG_EINVAL;
+    if ((excl_ptr == nullptr) != (excl_slot == nullptr) || excl_nnz < 0) return DG_EINVAL;
+    if (n_rows == 0) return DG_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (!excl_ptr || excl_nnz == 0) {  // nothing can be excluded: the unmasked kernel, the same bytes
+        hipLaunchKernelGGL(row_topk_kernel, dim3((unsigned)n_rows), dim3(64), a.t.cap * 8, st, a.t);
+        return dg::launch_status();
+    }
+    a.excl_ptr = excl_ptr;
+    a.excl_slot = excl_slot;
+    a.excl_nnz = excl_nnz;
+    hipLaunchKernelGGL(row_topk_excl_kernel, dim3((unsigned)n_rows), dim3(64), a.t.cap * 8 + dg::kWave * 4, st, a);
     return dg::launch_status();
 }

@@ -28,7 +28,9 @@ scorer launch (dg_decoder_score_seg_f32) and one segmented metrics call
 pair_profiles and top_relations answer the query the other way round — for given node pairs, the
 score of every relation of the edge type and each pair's best relations (NpPredictor._predictEdges
 per relation id, main/Predictor/NpPredictor.py:293-313): one launch over pairs × relations
-(dg_decoder_score_cross_f32) and a per-pair selection on the device (dg_row_topk_f32).
+(dg_decoder_score_cross_f32) and a per-pair selection on the device (dg_row_topk_f32), with
+top_relations(exclude=) outside each pair's known relations (dg_row_topk_excl_f32) — the reference's
+drop of the known edges on the host after _predictEdges.
 """
 from __future__ import annotations
 
@@ -403,8 +405,28 @@ def pair_profiles(sess, opt, placeholders, feed_dict, pairs, edge_type_ij, relat
     return _sigmoid_host(np.asarray(res), sigmoid)
 
 
+def _pair_exclusion(exclude, pairs, relations, num_relations: int, shape):
+    """top_relations' `exclude` as a sparse.PairExclusion of this query (None stays None): a
+    prebuilt one is checked against the query's pair and slot counts, anything else is built on
+    the host against `pairs` and `relations` with the edge type's table sizes `shape`."""
+    from .sparse import PairExclusion, pair_exclusion
+
+    if exclude is None:
+        return None
+    n_pairs = int(np.asarray(pairs).reshape(-1, 2).shape[0])
+    n_sel = int(num_relations) if relations is None else int(np.asarray(relations).size)
+    if isinstance(exclude, PairExclusion):
+        if (int(exclude.n_pairs), int(exclude.n_sel)) != (n_pairs, n_sel):
+            raise ValueError(f"exclude: lists of {exclude.n_pairs} pairs × {exclude.n_sel} slots, "
+                             f"the query has {n_pairs} × {n_sel}")
+        if exclude.ptr.shape[0] != n_pairs + 1:
+            raise ValueError("exclude: ptr must have one entry per pair and one more")
+        return exclude
+    return pair_exclusion(pairs, exclude, shape, relations, num_relations=num_relations)
+
+
 def top_relations(sess, opt, placeholders, feed_dict, pairs, edge_type_ij, k: int, relations=None,
-                  sigmoid: Optional[str] = None):
+                  sigmoid: Optional[str] = None, exclude=None):
     """For every pair its k highest-scoring relations of edge type (i, j) — "for this pair of
     drugs, which side effects?": numpy (scores [P, k], relations [P, k] int32, counts [P] int32),
     descending; slots past counts[p] hold −inf / −1.
@@ -417,11 +439,26 @@ def top_relations(sess, opt, placeholders, feed_dict, pairs, edge_type_ij, k: in
     returned array holds relation numbers, not positions.
 
     The ranking is by LOGIT, ties by the earlier position in `relations`; `sigmoid` (a key of
-    SIGMOID_MODES) only transforms the returned scores, as in top_candidates."""
+    SIGMOID_MODES) only transforms the returned scores, as in top_candidates.
+
+    `exclude` ranks every pair among the relations it is NOT yet known to have — the query for new
+    side effects.  It replaces NpPredictor._predictEdges per relation id followed by dropping the
+    known edges of each pair on the host (or, here, asking for k + known relations and filtering,
+    which copies the widest pair's columns back for every pair and ends at DG_TOPK_MAX_K): the
+    selection itself skips them (dg_row_topk_excl_f32).  None; a sparse.PairExclusion built for
+    these `pairs` and `relations` (sparse.pair_exclusion: kept across calls it is uploaded once per
+    device; its n_pairs and n_sel must match, ValueError); or what pair_exclusion takes — a
+    sparse.ExclusionCSR, or one entry per relation of the edge type as sparse.exclusion_csr takes
+    them (e.g. the training adjacencies), checked against the table sizes and turned into lists
+    on the host.  counts[p] becomes min(k, candidates − excluded candidates of pair p)."""
     k = int(k)
+    K = opt._model().edge_type2decoder.get(tuple(edge_type_ij))
+    K = K.num_types if K is not None else 0  # (an unknown edge type is refused below)
 
     def run(row_t, col_t, ri, ci, G, l, rel):
-        s, idx, n = kernels.decoder_top_relations(row_t, col_t, ri, ci, G, l, k, rel_idx=rel)
+        pe = _pair_exclusion(exclude, pairs, relations, K, (row_t.shape[0], col_t.shape[0]))
+        lists = pe.device(ri.device) if pe is not None else None
+        s, idx, n = kernels.decoder_top_relations(row_t, col_t, ri, ci, G, l, k, rel_idx=rel, exclude=lists)
         return torch.cat([s.view(torch.int32).reshape(-1), idx.reshape(-1), n])  # one copy back
 
     flat, rels = _profile_query("top_relations", sess, opt, placeholders, feed_dict, pairs, edge_type_ij,

@@ -1381,11 +1381,36 @@ def decoder_score_cross(row_table: torch.Tensor, col_table: torch.Tensor, row_id
     return out[:, :n_sel]
 
 
-def row_topk(x: torch.Tensor, topk: int, stream=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def _pair_lists(name, exclude, n):
+    """The (ptr, slot) exclusion lists of n rows, checked but for the device: int32 vectors,
+    contiguous, ptr of n + 1 entries (sparse.PairExclusion's layout)."""
+    if not isinstance(exclude, (tuple, list)) or len(exclude) != 2:
+        raise TypeError(f"{name}: exclude must be a (ptr, slot) pair of int32 device tensors")
+    ptr, slot = exclude
+    for t, nm in ((ptr, "exclude ptr"), (slot, "exclude slot")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{nm}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.dtype != torch.int32:
+            raise TypeError(f"{nm}: dtype {t.dtype}, expected {torch.int32}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{nm}: must be a contiguous vector")
+    if ptr.numel() != n + 1:
+        raise ValueError(f"{name}: exclude ptr must have one entry per row and one more ({n + 1})")
+    if slot.numel() >= 2**31:
+        raise ValueError(f"{name}: exclude slot exceeds int32 offsets")
+    return ptr, slot
+
+
+def row_topk(x: torch.Tensor, topk: int, stream=None, exclude=None
+             ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(values [n, topk] float32, idx [n, topk] int32, counts [n] int32): the topk highest entries
     of every row of the float32 device matrix x, descending (dg_row_topk_f32: higher value first,
     ties by smaller column, −0 as +0; counts = min(topk, columns), slots past it hold −inf / −1).
-    x may be a row-strided view (stride(1) == 1).  Asynchronous."""
+    x may be a row-strided view (stride(1) == 1).  Asynchronous.
+
+    exclude: None, or a (ptr, slot) pair of int32 device tensors, ptr [n + 1] and slot [nnz] —
+    row r is selected among the columns that slot[ptr[r] : ptr[r + 1]] (ascending, unique) does
+    not name (dg_row_topk_excl_f32), and counts[r] = min(topk, permitted columns)."""
     if not isinstance(x, torch.Tensor):
         raise TypeError(f"x: expected a torch.Tensor, got {type(x).__name__}")
     if x.dtype != torch.float32:
@@ -1397,23 +1422,34 @@ def row_topk(x: torch.Tensor, topk: int, stream=None) -> Tuple[torch.Tensor, tor
     topk = int(topk)
     if not 1 <= topk <= _lib.DG_TOPK_MAX_K:
         raise ValueError(f"row_topk: topk must be in [1, {_lib.DG_TOPK_MAX_K}]")
-    if not x.is_cuda:
-        raise ValueError("x: must be a device (HIP) tensor")
     n = x.shape[0]
+    if exclude is not None:
+        exclude = _pair_lists("row_topk", exclude, n)
+    _need_device([(x, "x")] + ([(exclude[0], "exclude ptr"), (exclude[1], "exclude slot")] if exclude else []))
+    if exclude and (exclude[0].device != x.device or exclude[1].device != x.device):
+        raise ValueError("row_topk: exclude must be on x's device")
     vals = torch.empty((n, topk), dtype=torch.float32, device=x.device)
     idx = torch.empty((n, topk), dtype=torch.int32, device=x.device)
     counts = torch.empty(n, dtype=torch.int32, device=x.device)
-    _row_topk_call(x, topk, vals, idx, counts, stream)
+    _row_topk_call(x, topk, vals, idx, counts, stream, exclude)
     return vals, idx, counts
 
 
-def _row_topk_call(x, topk, vals, idx, counts, stream) -> None:
+def _row_topk_call(x, topk, vals, idx, counts, stream, exclude=None, p0=0) -> None:
+    """The rows of x selected into vals / idx / counts; with `exclude` = (ptr, slot), row r under
+    list p0 + r: ptr is passed from entry p0 on with the whole of slot, whose offsets are absolute."""
     n = x.shape[0]
     if n == 0:
         return
-    check(_lib.load().dg_row_topk_f32(x.data_ptr(), max(x.stride(0), x.shape[1]), n, x.shape[1], topk,
-                                      vals.data_ptr(), idx.data_ptr(), counts.data_ptr(), None, 0,
-                                      _stream_ptr(stream)), "dg_row_topk_f32")
+    ld = max(x.stride(0), x.shape[1])
+    if exclude is None or exclude[1].numel() == 0:  # (an empty tensor has no address: nothing is excluded)
+        check(_lib.load().dg_row_topk_f32(x.data_ptr(), ld, n, x.shape[1], topk, vals.data_ptr(), idx.data_ptr(),
+                                          counts.data_ptr(), None, 0, _stream_ptr(stream)), "dg_row_topk_f32")
+        return
+    ptr, slot = exclude
+    check(_lib.load().dg_row_topk_excl_f32(x.data_ptr(), ld, n, x.shape[1], topk, ptr.data_ptr() + 4 * p0,
+                                           slot.data_ptr(), slot.numel(), vals.data_ptr(), idx.data_ptr(),
+                                           counts.data_ptr(), _stream_ptr(stream)), "dg_row_topk_excl_f32")
 
 
 def top_relations_chunks(n_pairs: int, n_sel: int, max_workspace_bytes: int):
@@ -1432,7 +1468,7 @@ def top_relations_chunks(n_pairs: int, n_sel: int, max_workspace_bytes: int):
 def decoder_top_relations(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: torch.Tensor,
                           col_idx: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor], topk: int,
                           rel_idx: Optional[torch.Tensor] = None, max_workspace_bytes: int = 64 << 20,
-                          stream=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                          stream=None, exclude=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(scores [P, topk] float32, slots [P, topk] int32, counts [P] int32): for every pair the topk
     highest-scoring slots of decoder_score_cross's row (operands and rel_idx as there; a slot is a
     position of rel_idx, or the relation itself when rel_idx is None), in row_topk's order.
@@ -1441,13 +1477,23 @@ def decoder_top_relations(row_table: torch.Tensor, col_table: torch.Tensor, row_
     most max_workspace_bytes (at least 32 rows) and each chunk is selected into its rows of the
     outputs, so no P×n_sel matrix exists at any time.  A pair's scores do not depend on its
     neighbours and the selection order is total: the result is the same, bytes and all, whatever
-    the bound."""
+    the bound.
+
+    exclude: None, or row_topk's (ptr, slot) pair with one list per PAIR (sparse.PairExclusion's
+    layout): pair p is ranked among the slots its list does not name, counts[p] = min(topk,
+    n_sel − its entries).  A chunk reads ptr from its first pair on and the whole of slot — the
+    offsets are absolute — so the bound still does not change a byte."""
     ops, n, n_sel = _cross_operands("decoder_top_relations", row_table, col_table, row_idx, col_idx, G, l, rel_idx)
     topk = int(topk)
     if not 1 <= topk <= _lib.DG_TOPK_MAX_K:
         raise ValueError(f"decoder_top_relations: topk must be in [1, {_lib.DG_TOPK_MAX_K}]")
-    _need_device(list(ops.tabs) + [(row_idx, "row_idx"), (col_idx, "col_idx"), (rel_idx, "rel_idx")])
+    if exclude is not None:
+        exclude = _pair_lists("decoder_top_relations", exclude, n)
+    _need_device(list(ops.tabs) + [(row_idx, "row_idx"), (col_idx, "col_idx"), (rel_idx, "rel_idx")]
+                 + ([(exclude[0], "exclude ptr"), (exclude[1], "exclude slot")] if exclude else []))
     dev = G.device
+    if exclude and (exclude[0].device != dev or exclude[1].device != dev):
+        raise ValueError("decoder_top_relations: exclude must be on the operands' device")
     vals = torch.empty((n, topk), dtype=torch.float32, device=dev)
     idx = torch.empty((n, topk), dtype=torch.int32, device=dev)
     counts = torch.empty(n, dtype=torch.int32, device=dev)
@@ -1457,7 +1503,7 @@ def decoder_top_relations(row_table: torch.Tensor, col_table: torch.Tensor, row_
     for p0, p1 in chunks:
         m = p1 - p0
         _score_cross_call(ops, row_idx, col_idx, rel_idx, n_sel, p0, m, ws, stream)
-        _row_topk_call(ws[:m], topk, vals[p0:p1], idx[p0:p1], counts[p0:p1], stream)
+        _row_topk_call(ws[:m], topk, vals[p0:p1], idx[p0:p1], counts[p0:p1], stream, exclude, p0)
     return vals, idx, counts
 
 

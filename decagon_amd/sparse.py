@@ -223,6 +223,101 @@ def exclusion_csr(mats_or_coo_list, shape) -> ExclusionCSR:
 
 
 @dataclass
+class PairExclusion:
+    """Per-pair exclusion lists of dg_row_topk_excl_f32, pair-major: queried pair p skips the slots
+    slot[ptr[p] : ptr[p + 1]], ascending and unique, each in [0, n_sel) — a slot is a position of
+    the query's `relations` (the relation itself when that is None).  The layout the selection
+    kernel reads once, coalesced, next to the pair's row of scores."""
+
+    ptr: np.ndarray   # int32 [n_pairs + 1]
+    slot: np.ndarray  # int32 [nnz]
+    n_pairs: int
+    n_sel: int
+    _on_device: dict = field(default_factory=dict, repr=False, compare=False)
+
+    @property
+    def nnz(self) -> int:
+        return int(self.slot.shape[0])
+
+    def device(self, device):
+        """(ptr, slot) as int32 tensors on `device`, uploaded on first use and kept: a query
+        repeated on a changing model uploads the lists once."""
+        import torch
+
+        key = str(torch.device(device))
+        if key not in self._on_device:
+            self._on_device[key] = (torch.from_numpy(np.ascontiguousarray(self.ptr, np.int32)).to(device),
+                                    torch.from_numpy(np.ascontiguousarray(self.slot, np.int32)).to(device))
+        return self._on_device[key]
+
+
+def pair_exclusion(pairs, exclude, shape, relations=None, num_relations: Optional[int] = None) -> PairExclusion:
+    """The exclusion lists of the pairs of one evaluate.top_relations query: pair p lists every
+    position s with pairs[p] in the exclusion set of relation relations[s] (default: every
+    relation, in order).  `exclude` is an ExclusionCSR or what exclusion_csr takes — one entry per
+    relation of the edge type (e.g. the training adjacencies); `shape` = (N_i, N_j).  A repeated
+    pair gets its own, equal, list; a relation listed twice is excluded at both positions.
+    ValueError: a pair, an exclusion index or a relation out of range, a shape that is not
+    `shape`, a number of relation entries other than num_relations (when given), nnz ≥ 2³¹.
+
+    Built from the edges, not from pairs × slots: each listed relation's keys r·N_j + c are
+    looked up (searchsorted) in the unique keys of the pairs, the hits expanded to the repeats of
+    their pair, and all (pair, slot) sorted."""
+    n_r, n_c = int(shape[0]), int(shape[1])
+    ex = exclude if isinstance(exclude, ExclusionCSR) else exclusion_csr(exclude, (n_r, n_c))
+    if (ex.n_rows, ex.n_cols) != (n_r, n_c):
+        raise ValueError(f"exclusion shape {(ex.n_rows, ex.n_cols)} != {(n_r, n_c)}")
+    K = int(ex.n_rels)
+    if num_relations is not None and K != int(num_relations):
+        raise ValueError(f"{K} exclusion entries for {int(num_relations)} relations")
+    pr = np.asarray(pairs, dtype=np.int64)
+    if pr.size == 0:
+        pr = pr.reshape(0, 2)
+    if pr.ndim != 2 or pr.shape[1] != 2:
+        raise ValueError("pairs must be an [n, 2] array")
+    P = pr.shape[0]
+    if P and (pr.min() < 0 or pr[:, 0].max() >= n_r or pr[:, 1].max() >= n_c):
+        raise ValueError(f"pair out of range for shape {(n_r, n_c)}")
+    rels = np.arange(K, dtype=np.int64) if relations is None else np.asarray(relations, np.int64).reshape(-1)
+    if rels.size < 1:
+        raise ValueError("no relations listed")
+    if rels.min() < 0 or rels.max() >= K:
+        raise ValueError(f"relation outside [0, {K})")
+    n_sel = int(rels.size)
+    if P >= 2**31 - 1:
+        raise ValueError("too many pairs for int32 offsets")
+
+    # the pairs grouped by their unique key: key u is pairs order[start[u] : start[u] + reps[u]]
+    uniq, inv = np.unique(pr[:, 0] * n_c + pr[:, 1], return_inverse=True)
+    inv = inv.reshape(-1)
+    order = np.argsort(inv, kind="stable")
+    reps = np.bincount(inv, minlength=uniq.size)
+    start = np.cumsum(reps) - reps
+    rowptr, col = ex.rowptr.astype(np.int64), ex.col.astype(np.int64)
+    rows = np.arange(n_r, dtype=np.int64)
+    hits = {}  # relation → the pairs in its set (a relation listed twice is looked up once)
+    parts, total = [], 0
+    for s, k in enumerate(rels.tolist()):
+        if k not in hits:
+            rp = rowptr[k * n_r:(k + 1) * n_r + 1]
+            keys = np.repeat(rows, np.diff(rp)) * n_c + col[rp[0]:rp[-1]]
+            pos = np.searchsorted(uniq, keys)
+            u = pos[pos < uniq.size]
+            u = u[uniq[u] == keys[pos < uniq.size]]
+            n = reps[u]
+            within = np.arange(int(n.sum()), dtype=np.int64) - np.repeat(np.cumsum(n) - n, n)
+            hits[k] = order[np.repeat(start[u], n) + within]
+        total += hits[k].size
+        if total >= 2**31:
+            raise ValueError("pair exclusion lists exceed int32 offsets")
+        parts.append(hits[k] * n_sel + s)
+    lin = np.sort(np.concatenate(parts)) if parts else np.zeros(0, np.int64)  # by (pair, slot); unique
+    ptr = np.zeros(P + 1, np.int64)
+    np.cumsum(np.bincount(lin // n_sel, minlength=P), out=ptr[1:])
+    return PairExclusion(ptr.astype(np.int32), (lin % n_sel).astype(np.int32), P, n_sel)
+
+
+@dataclass
 class MergedCSR:
     """A group's relations in the chunk-merged layout of dg_rel_group (decagon_hip.h):
     for chunk c and row r the nonzeros of every relation of the chunk, contiguous, at

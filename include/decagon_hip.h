@@ -1061,6 +1061,21 @@ int32_t dg_seg_tile_lookup(const int32_t* seg_ptr, int32_t n_seg, int32_t tile, 
  * 1 <= n_cols < 2^31.  One wave per row keeps the list in LDS: no workspace is needed —
  * dg_row_topk_workspace returns 0 and a NULL workspace is accepted.  Asynchronous; n_rows == 0
  * succeeds without a launch.
+ *
+ * dg_row_topk_excl_f32: dg_row_topk_f32 over the columns of row r that are NOT named by
+ * excl_slot[excl_ptr[r] : excl_ptr[r+1]] — a pair's known relations, which the reference drops on
+ * the host after NpPredictor._predictEdges per relation id.  excl_ptr is device int32
+ * [n_rows + 1], excl_slot device int32 [excl_nnz], each row's entries ascending and unique.
+ * Order, −0 handling and −inf / −1 past the count are those of dg_row_topk_f32; out_count[r] is
+ * the number of slots written, min(topk, permitted columns of row r), 0 when every column is
+ * excluded.  One wave per row merges the list into its single pass over the row (the list is read
+ * once, coalesced; the running top-k stays in LDS): no workspace.  A row's range is clamped to
+ * [0, excl_nnz) and a non-increasing excl_ptr pair is an empty list; an entry outside
+ * [0, n_cols) excludes nothing; an unsorted list leaves unspecified which of its entries apply;
+ * no input makes the kernel read or write out of range.  Both pointers NULL (or excl_nnz == 0)
+ * mean no exclusion, the bytes of dg_row_topk_f32; exactly one NULL, or excl_nnz < 0, is
+ * DG_EINVAL (the rule of dg_decoder_topk_f32), as is everything dg_row_topk_f32 rejects.
+ * Asynchronous, allocates nothing, reads nothing on the host (graph capture).
  * -------------------------------------------------------------------------------------- */
 #define DG_CROSS_MAX_OUT (1ll << 38)
 int dg_decoder_score_cross_f32(const float* row_table, int64_t ld_row, int32_t n_rows,
@@ -1074,6 +1089,9 @@ int64_t dg_row_topk_workspace(int32_t n_rows, int32_t n_cols, int32_t topk);
 int dg_row_topk_f32(const float* x, int64_t ld, int32_t n_rows, int32_t n_cols, int32_t topk,
                     float* out_val, int32_t* out_idx, int32_t* out_count, void* workspace,
                     int64_t workspace_bytes, void* stream);
+int dg_row_topk_excl_f32(const float* x, int64_t ld, int32_t n_rows, int32_t n_cols, int32_t topk,
+                         const int32_t* excl_ptr, const int32_t* excl_slot, int32_t excl_nnz,
+                         float* out_val, int32_t* out_idx, int32_t* out_count, void* stream);
 
 /* --------------------------------------------------------------------------------------
  * The decoder backward of the hinge cost for every relation's batch of one edge type in one pass
