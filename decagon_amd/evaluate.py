@@ -80,30 +80,17 @@ def _stacked_latents(ctx: RunContext, dec, d: int):
     parameter buffer: DEDICOM the shared R [d, d] and local_variation_k at stride d ([K, d]);
     Bilinear relation_k at stride d·d ([K, d, d]); DistMult's diagonals and InnerProduct's
     identity expanded once per run to dense G, as runtime.latent_operands does."""
-    K = dec.num_types
-    specs = [dec.latent(k) for k in range(K)]
-    gk, _, lk, _ = specs[0]
-
-    def stack(vars_, per):  # K equally spaced variables of `per` floats → one [K, per] view
-        off0 = (vars_[0].tensor.data_ptr() - dec.flat.data_ptr()) // 4
-        for k, v in enumerate(vars_):
-            if (v.tensor.data_ptr() - dec.flat.data_ptr()) // 4 != off0 + k * per or v.tensor.numel() != per:
-                raise RuntimeError("decoder variables are not equally spaced in the flat buffer")
-        return dec.flat[off0:off0 + K * per].view(K, per)
-
-    if gk == "dense":
-        gvars = [s[1] for s in specs]
-        if all(v is gvars[0] for v in gvars):
-            G = gvars[0].tensor.contiguous()
-        else:
-            G = stack(gvars, d * d).view(K, d, d)
+    lay = dec.layout
+    if lay.g_kind == "dense":
+        G = lay.stacked(dec.flat, "G")
+        G = G.view(d, d) if lay.G[3] == 1 else G.view(-1, d, d)
     else:
-        key = ("topk_G", gk, id(dec), d)
+        key = ("topk_G", lay.g_kind, id(dec), d)
         if key not in ctx.cache:
-            ctx.cache[key] = (torch.eye(d, device=ctx.session.device) if gk == "eye"
-                              else torch.diag_embed(stack([s[1] for s in specs], d)).contiguous())
+            ctx.cache[key] = (torch.eye(d, device=ctx.session.device) if lay.g_kind == "eye"
+                              else torch.diag_embed(lay.stacked(dec.flat, "G")).contiguous())
         G = ctx.cache[key]
-    l = stack([s[3] for s in specs], d) if lk == "diag" else None
+    l = lay.stacked(dec.flat, "l") if lay.l_kind == "diag" else None
     return G, l
 
 
@@ -111,6 +98,25 @@ def first_relation(model, edge_type_ij) -> int:
     """The flat index (over all edge types, in model.edge_types' order) of relation 0 of an edge type."""
     ets = list(model.edge_types)
     return sum(model.edge_types[et] for et in ets[:ets.index(tuple(edge_type_ij))])
+
+
+def _edge_type_record(ctx: RunContext, opt, model, edge_type_ij) -> dict:
+    """What a run derives from an edge type's unchanging place among the optimizer's relations, per
+    (optimizer, edge type) in the session caches: "first", its first_relation, and "latents", the
+    set of its relations' latent nodes."""
+    et = tuple(edge_type_ij)
+    key = ("edge_type_record", id(opt), et)
+    cache = ctx.session.caches
+    if key not in cache:
+        first = first_relation(model, et)
+        rels = slice(first, first + model.edge_types[et])
+        cache[key] = {"first": first, "latents": frozenset(opt.latent_inters[rels]) | frozenset(opt.latent_varies[rels])}
+    return cache[key]
+
+
+def latent_fed(ctx: RunContext, opt, model, edge_type_ij) -> bool:
+    """Whether a latent matrix of any relation of the edge type is fed in this run."""
+    return not _edge_type_record(ctx, opt, model, edge_type_ij)["latents"].isdisjoint(ctx.feeds)
 
 
 def _edge_type_decoder(model, edge_type_ij, sigmoid):
@@ -128,10 +134,8 @@ def _edge_type_operands(name, ctx: RunContext, opt, model, edge_type_ij):
     matrix is refused."""
     i, j = edge_type_ij
     dec = model.edge_type2decoder[i, j]
-    first = first_relation(model, (i, j))
-    for r in range(first, first + dec.num_types):
-        if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
-            raise ValueError(f"{name} reads the decoder's variables; a latent matrix is fed")
+    if latent_fed(ctx, opt, model, (i, j)):
+        raise ValueError(f"{name} reads the decoder's variables; a latent matrix is fed")
     row_t, col_t = opt._tables(ctx, i, j)
     G, l = _stacked_latents(ctx, dec, row_t.shape[1])
     return dec.num_types, row_t, col_t, G, l

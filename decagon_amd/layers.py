@@ -12,7 +12,8 @@ DecagonModel passes, model.py:71/83/99/...) and relu are supported on the device
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -234,6 +235,50 @@ class GraphConvolutionMulti(_GraphConvBase):
         return Node(f"{self.name}/out", fn)
 
 
+@dataclass(frozen=True)
+class DecoderLayout:
+    """Where a decoder's variables sit in its flat buffer, in floats: `vars` name -> (offset,
+    numel); `G` and `l`, the relations' latent variables as a stack (offset, per, stride, count) —
+    count variables of `per` floats, `stride` apart; count is 1 for a G all relations share — or
+    None where the kind is "eye"; and the kinds as `latent(k)` reports them.  Every method takes
+    ANY buffer laid out like `flat`: the parameters themselves, or their gradients
+    (torch.zeros_like(flat))."""
+    vars: Dict[str, Tuple[int, int]]
+    G: Optional[Tuple[int, int, int, int]]
+    l: Optional[Tuple[int, int, int, int]]
+    g_kind: str
+    l_kind: str
+
+    def var(self, buf: torch.Tensor, name: str) -> torch.Tensor:
+        """The slice of `buf` that belongs to variable `name`."""
+        off, n = self.vars[name]
+        return buf[off:off + n]
+
+    def relation(self, buf: torch.Tensor, which: str, k: int) -> torch.Tensor:
+        """Relation k's slice of the `which` ("G" or "l") stack; a shared G's for every k."""
+        off, per, stride, count = getattr(self, which)
+        off += k * stride if count > 1 else 0
+        return buf[off:off + per]
+
+    def stacked(self, buf: torch.Tensor, which: str) -> torch.Tensor:
+        """The whole `which` stack as one [count, per] view of `buf`."""
+        off, per, stride, count = getattr(self, which)
+        if count > 1 and stride != per:
+            raise RuntimeError("decoder variables are not equally spaced in the flat buffer")
+        return buf[off:off + count * per].view(count, per)
+
+    def grad_outputs(self, gbuf: torch.Tensor, k: Optional[int] = None) -> Dict[str, Optional[torch.Tensor]]:
+        """The decoder-gradient kernels' outputs dG / dG_diag / dl as slices of the gradient buffer
+        `gbuf`: relation k's, or (k None) the stacked views of all relations."""
+        cut = (lambda w: self.stacked(gbuf, w)) if k is None else (lambda w: self.relation(gbuf, w, k))
+        out = {"dG": None, "dl": None, "dG_diag": None}
+        if self.g_kind != "eye":
+            out["dG" if self.g_kind == "dense" else "dG_diag"] = cut("G")
+        if self.l_kind == "diag":
+            out["dl"] = cut("l")
+        return out
+
+
 class _DecoderBase(MultiLayer):
     """Decoders own parameters; DecagonModel reads them into latent_inters/latent_varies
     (model.py:116-137).  `_call` (dead code in the reference, §0.4 of SURVEY) is provided:
@@ -247,19 +292,35 @@ class _DecoderBase(MultiLayer):
 
     def _make_vars(self, init_fns) -> None:
         """All of the decoder's variables as views of ONE flat device buffer (`self.flat`),
-        each starting 16-byte aligned — so the optimizer updates a decoder in one segment.
+        each starting 16-byte aligned — so the optimizer updates a decoder in one segment —
+        and `self.layout`, where each one sits (DecoderLayout; `flat` is assigned only here).
         init_fns: name -> initializer (drawn once here, again by global_variables_initializer)."""
-        arrays = {name: fn() for name, fn in init_fns.items()}
+        arrays = {name: np.ascontiguousarray(fn(), np.float32) for name, fn in init_fns.items()}
         offs, off = {}, 0
         for name, a in arrays.items():
-            offs[name] = off
-            off += -(-int(np.asarray(a).size) // 4) * 4
+            offs[name] = (off, a.size)
+            off += -(-a.size // 4) * 4
         self.flat = torch.zeros(off, dtype=torch.float32, device=runtime.param_device())
         for name, a in arrays.items():
-            a = np.ascontiguousarray(a, np.float32)
-            view = self.flat[offs[name]:offs[name] + a.size].view(a.shape)
+            view = self.flat[offs[name][0]:offs[name][0] + a.size].view(a.shape)
             view.copy_(torch.from_numpy(a))
             self.vars[name] = Variable(view, f"{self._scope()}/{name}:0", initializer=init_fns[name])
+        names = {id(v): name for name, v in self.vars.items()}
+        specs = [self.latent(k) for k in range(self.num_types)]
+
+        def stack(c):  # column c of latent(k) over all k: one shared variable, or one per relation
+            at = [offs[names[id(sp[c])]] for sp in specs]
+            if all(sp[c] is specs[0][c] for sp in specs):
+                at = at[:1]
+            off0, per = at[0]
+            stride = at[1][0] - off0 if len(at) > 1 else per
+            if any(a != (off0 + k * stride, per) for k, a in enumerate(at)):
+                raise RuntimeError("a decoder's latent variables differ in size or spacing")
+            return off0, per, stride, len(at)
+
+        gk, _, lk, _ = specs[0] if specs else ("eye", None, "eye", None)
+        self.layout = DecoderLayout(offs, stack(1) if gk != "eye" else None, stack(3) if lk != "eye" else None,
+                                    gk, lk)
 
     def latent(self, k: int):
         """(G kind, G variable or None, L kind, L variable or None) for relation k."""

@@ -133,7 +133,6 @@ class DecagonModel(Model):
 
         self.latent_inters: List[_LatentNode] = []
         self.latent_varies: List[_LatentNode] = []
-        self._latent_spec = []
         for edge_type in self.edge_types:
             dec = self.edge_type2decoder[edge_type]
             for k in range(self.edge_types[edge_type]):
@@ -141,7 +140,6 @@ class DecagonModel(Model):
                 r = len(self.latent_inters)
                 self.latent_inters.append(_LatentNode(f"{self.name}/latent_inter_{r}", gk, gv, h2))
                 self.latent_varies.append(_LatentNode(f"{self.name}/latent_vary_{r}", lk, lv, h2))
-                self._latent_spec.append((gk, gv, lk, lv))
 
     def _variables(self):
         out = []

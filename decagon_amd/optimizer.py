@@ -227,38 +227,26 @@ class DecagonOptimizer:
             t.zero_()
         return grads
 
-    @staticmethod
-    def _grad_view(dec, gflat: torch.Tensor, var) -> torch.Tensor:
-        """The slice of a decoder's flat gradient buffer that belongs to `var`."""
-        off = (var.tensor.data_ptr() - dec.flat.data_ptr()) // 4
-        return gflat[off:off + var.tensor.numel()]
-
     def _decoder_grads(self, ctx: RunContext, model, e: int, rt: int, ct: int):
         """Zeroed gradient buffers of every decoder, the batch relation's entries filled
         (TF's gather over the stacked latent lists gives the others dense zeros)."""
         grads = self._decoder_grad_buffers(ctx, model)
         i, j, k = self._rel_of[e]
-        dec = model.edge_type2decoder[i, j]
-        gview = lambda var: self._grad_view(dec, grads[i, j], var)  # noqa: E731
-        gk, gv, lk, lv = model._latent_spec[e]
-        fed = ctx.is_fed(self.latent_inters[e]) or ctx.is_fed(self.latent_varies[e])
-        out = {"dG": None, "dl": None, "dG_diag": None}
-        if not fed:
-            if gk == "dense":
-                out["dG"] = gview(gv)
-            elif gk == "diag":
-                out["dG_diag"] = gview(gv)
-            if lk == "diag":
-                out["dl"] = gview(lv)
-        return grads, out
+        if ctx.is_fed(self.latent_inters[e]) or ctx.is_fed(self.latent_varies[e]):
+            return grads, {"dG": None, "dl": None, "dG_diag": None}
+        return grads, model.edge_type2decoder[i, j].layout.grad_outputs(grads[i, j], k)
 
-    def _train(self, ctx: RunContext, apply: bool):
-        """One training step (apply) or the gradients only (compute_gradients)."""
+    def _check_training(self, ctx: RunContext) -> None:
+        """What every training node refuses before it does anything."""
         if not ctx.training:
             raise RuntimeError("training ops must be fetched through Session.run")
         for nd in (self.outputs, self.neg_outputs, self.cost):
             if ctx.is_fed(nd):
                 raise InvalidArgumentError(f"{nd.name} is fed: the cost's gradient does not reach the model")
+
+    def _train(self, ctx: RunContext, apply: bool):
+        """One training step (apply) or the gradients only (compute_gradients)."""
+        self._check_training(ctx)
         model = self._model()
         fwd, tp = self._train_plan(ctx, model)
         pos, neg, _, negs_dev = ctx.value(self._decode)
@@ -319,10 +307,8 @@ class DecagonOptimizer:
             for k in range(lay.num_types):
                 out.append((gW2[et][k], lay.vars["weights_%d" % k].tensor))
         for et, dec in model.edge_type2decoder.items():
-            for var in dec.vars.values():
-                off = (var.tensor.data_ptr() - dec.flat.data_ptr()) // 4
-                out.append((dec_grads[et][off:off + var.tensor.numel()].view(var.tensor.shape).clone(),
-                            var.tensor.clone()))
+            for name, var in dec.vars.items():
+                out.append((dec.layout.var(dec_grads[et], name).view(var.tensor.shape).clone(), var.tensor.clone()))
         return [(g.clone(), v.clone()) for g, v in out]
 
     def _hinge_loss(self, aff, neg_aff):

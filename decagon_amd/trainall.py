@@ -28,8 +28,8 @@ import numpy as np
 import torch
 
 from . import kernels
-from .epochs import DeviceBatches, _items
-from .evaluate import _stacked_latents, first_relation
+from .epochs import DeviceBatches, TypeBatch, _items
+from .evaluate import _edge_type_record, _stacked_latents, latent_fed
 from .graph import InvalidArgumentError, Node, RunContext
 
 EdgeType = Tuple[int, int]
@@ -144,58 +144,44 @@ def _stage(name: str, t0: float) -> float:
     return t1
 
 
-def _device_view(batches: DeviceBatches, edge_types) -> Dict[EdgeType, dict]:
-    """A DeviceBatches in pack_batches' terms: the host seg_ptr / seg_rel (K small ints, what the
-    checks and fed negatives read) and the device arrays under "dev"."""
-    out = {}
+def type_batch(p: Dict[str, np.ndarray], negs: Optional[np.ndarray], device):
+    """One edge type's packed host batches (pack_batches) as an epochs.TypeBatch on `device`, and
+    its fed negatives there (`negs`, in segment order; None stays None) — one upload:
+    [rows | cols | (negatives) | seg_ptr | seg_ptr[1:] + n | seg_rel | seg_rel]."""
+    n, n_seg = int(p["seg_ptr"][-1]), len(p["seg_rel"])
+    host = np.concatenate([p["rows"], p["cols"]] + ([negs] if negs is not None else []) +
+                          [p["seg_ptr"], p["seg_ptr"][1:] + n, p["seg_rel"], p["seg_rel"]]).astype(np.int32)
+    buf = torch.from_numpy(host).to(device)
+    o = buf.numel() - (4 * n_seg + 1)
+    seg2, rel2 = buf[o:o + 2 * n_seg + 1], buf[o + 2 * n_seg + 1:]
+    tb = TypeBatch(buf[:n], buf[n:2 * n], seg2[:n_seg + 1], rel2[:n_seg], n, n_seg, seg2, rel2, p["seg_rel"])
+    return tb, (buf[2 * n:3 * n] if negs is not None else None)
+
+
+def _device_types(batches: DeviceBatches, edge_types, neg_samples, shapes, device):
+    """A DeviceBatches' TypeBatches as they are, each with its fed negatives on `device` (or None)."""
     for et, tb in batches.items():
         if et not in edge_types:
             raise ValueError(f"unknown edge type {et}")
         if tb.n_seg > edge_types[et] or (tb.n_seg and int(tb.rel_host.max()) >= edge_types[et]):
             raise ValueError(f"edge type {et}: the batches list relations it does not have")
-        out[et] = {"seg_ptr": np.arange(tb.n_seg + 1, dtype=np.int64) * batches.batch_size, "seg_rel": tb.rel_host,
-                   "dev": tb}
-    return out
+    if neg_samples is None:
+        return {et: (tb, None) for et, tb in batches.items()}
+    segs = {et: {"seg_ptr": np.arange(tb.n_seg + 1, dtype=np.int64) * batches.batch_size, "seg_rel": tb.rel_host}
+            for et, tb in batches.items()}
+    negs = _negatives(neg_samples, segs, shapes)
+    return {et: (tb, torch.from_numpy(negs[et]).to(device)) for et, tb in batches.items()}
 
 
-def _decoder_meta(ctx: RunContext, opt, model, et: EdgeType) -> dict:
-    """What a step derives from an edge type's unchanging decoder layout, per (optimizer, edge type)
-    in the session cache: the global slot of its first relation, the set of its latent nodes, and
-    the offsets of the variables' gradient slices in the decoder's flat buffer — in place of a walk
-    over dec.latent(k) for all K every step.  Rebuilt if the flat buffer moved."""
-    key = ("trainall_meta", id(opt), et)
-    cache = ctx.session.caches
-    dec = model.edge_type2decoder[et]
-    meta = cache.get(key)
-    if meta is None or meta["flat_ptr"] != dec.flat.data_ptr():
-        K = model.edge_types[et]
-        first = first_relation(model, et)
-        specs = [dec.latent(k) for k in range(K)]
-        gk, lk = specs[0][0], specs[0][2]
-        off = lambda c: (specs[0][c].tensor.data_ptr() - dec.flat.data_ptr()) // 4  # noqa: E731
-        slices = {}
-        if gk == "dense":
-            shared = all(sp[1] is specs[0][1] for sp in specs)
-            slices["dG"] = (off(1), 1 if shared else K)
-        elif gk == "diag":
-            slices["dG_diag"] = (off(1), K)
-        if lk == "diag":
-            slices["dl"] = (off(3), K)
-        lat = frozenset(opt.latent_inters[first:first + K]) | frozenset(opt.latent_varies[first:first + K])
-        meta = cache[key] = {"flat_ptr": dec.flat.data_ptr(), "first": first, "latents": lat,
-                             "grad_slices": slices, "views": gk == "dense"}
-    return meta
-
-
-def _cached_latents(ctx: RunContext, meta: dict, dec, d: int):
-    """_stacked_latents, kept across steps where (G, l) are views of the decoder's flat buffer
-    (DEDICOM, Bilinear: the optimizer updates it in place); the expanded forms depend on the
-    variables' values and are rebuilt per run."""
-    if not meta["views"]:
+def _cached_latents(ctx: RunContext, rec: dict, dec, d: int):
+    """_stacked_latents, kept across steps (in the edge type's record) where (G, l) are views of the
+    decoder's flat buffer (DEDICOM, Bilinear: the optimizer updates it in place); the expanded forms
+    depend on the variables' values and are rebuilt per run."""
+    if dec.layout.g_kind != "dense":
         return _stacked_latents(ctx, dec, d)
-    if meta.get("Gl_d") != d:
-        meta["Gl"], meta["Gl_d"] = _stacked_latents(ctx, dec, d), d
-    return meta["Gl"]
+    if rec.get("Gl_d") != d:
+        rec["Gl"], rec["Gl_d"] = _stacked_latents(ctx, dec, d), d
+    return rec["Gl"]
 
 
 def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None, apply: bool = True):
@@ -215,10 +201,13 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
 
     batches may also be an epochs.DeviceBatches (EdgeBatches.batch): the step then uses its device
     arrays as they are — nothing is packed, no index array is uploaded (fed negatives apart) and
-    nothing is read back before the cost — and takes the decoder's operand views and gradient
-    slices from a per-(optimizer, edge type) cache in place of a walk over every relation's
-    variables.  It runs the same kernels on the same indices: cost and gradients equal the host
-    form's on EdgeBatches.host_batch bit for bit.
+    nothing is read back before the cost.  Host batches are packed and uploaded once per edge type
+    into the same form (type_batch) before the run; from there both forms take one path.  It takes
+    the edge type's latent nodes and first relation from a per-(optimizer, edge type) record in the
+    session caches, the operand views of DEDICOM and Bilinear from the same record, and the
+    gradient slices from the decoder's layout — no walk over every relation's variables.  The same
+    kernels run on the same indices: cost and gradients of the device form equal the host form's
+    on EdgeBatches.host_batch bit for bit.
 
     NotImplementedError for a sharded session; InvalidArgumentError when a decoder latent of a
     trained edge type, or `outputs` / `neg_outputs` / `cost`, is fed."""
@@ -227,34 +216,22 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
         raise NotImplementedError("train_step_all runs on one GPU (the session is sharded)")
     shapes = {et: tuple(int(x) for x in opt.edge_type2dim[et][0]) for et in model.edge_types}
     if isinstance(batches, DeviceBatches):
-        packed = _device_view(batches, model.edge_types)
+        types = _device_types(batches, model.edge_types, neg_samples, shapes, sess.device)
     else:
         packed = pack_batches(batches, model.edge_types, shapes)
-    if neg_samples is None:
-        for et, p in packed.items():
-            if len(set(np.diff(p["seg_ptr"]).tolist())) > 1:
-                raise ValueError(f"edge type {et}: batch sizes differ between relations; feed neg_samples")
-        negs_host = None
-    else:
-        negs_host = _negatives(neg_samples, packed, shapes)
+        if neg_samples is None:
+            for et, p in packed.items():
+                if len(set(np.diff(p["seg_ptr"]).tolist())) > 1:
+                    raise ValueError(f"edge type {et}: batch sizes differ between relations; feed neg_samples")
+        negs_host = _negatives(neg_samples, packed, shapes) if neg_samples is not None else {}
+        types = {et: type_batch(p, negs_host.get(et), sess.device) for et, p in packed.items()}
 
     def fn(ctx: RunContext):
-        if not ctx.training:
-            raise RuntimeError("training ops must be fetched through Session.run")
-        for nd in (opt.outputs, opt.neg_outputs, opt.cost):
-            if ctx.is_fed(nd):
-                raise InvalidArgumentError(f"{nd.name} is fed: the cost's gradient does not reach the model")
+        opt._check_training(ctx)
         t0 = time.perf_counter()
-        for et, p in packed.items():
-            if "dev" in p:  # (the cached set of the edge type's latent nodes against the few feeds)
-                lat = _decoder_meta(ctx, opt, model, et)["latents"]
-                if any(nd in lat for nd in ctx.feeds):
-                    raise InvalidArgumentError("train_step_all trains the decoder's variables; a latent matrix is fed")
-                continue
-            first = first_relation(model, et)
-            for r in range(first, first + model.edge_types[et]):
-                if ctx.is_fed(opt.latent_inters[r]) or ctx.is_fed(opt.latent_varies[r]):
-                    raise InvalidArgumentError("train_step_all trains the decoder's variables; a latent matrix is fed")
+        for et in types:
+            if latent_fed(ctx, opt, model, et):
+                raise InvalidArgumentError("train_step_all trains the decoder's variables; a latent matrix is fed")
         fwd, tp = opt._train_plan(ctx, model)
         if tp.sharded:
             raise NotImplementedError("train_step_all runs on one GPU (the plan is sharded)")
@@ -262,77 +239,35 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
         dec_grads = opt._decoder_grad_buffers(ctx, model)
         t0 = _stage("forward", t0)
         costs, work = [], []
-        for et, p in packed.items():
+        for et, (tb, negs) in types.items():
             i, j = et
-            n, n_seg = int(p["seg_ptr"][-1]), len(p["seg_rel"])
+            n, n_seg, rows, cols = tb.n, tb.n_seg, tb.rows, tb.cols
             if n == 0:
                 continue
-            K = model.edge_types[et]
             dec = model.edge_type2decoder[et]
             row_t, col_t = opt._tables(ctx, i, j)
-            d = row_t.shape[1]
-            fed = negs_host is not None
-            tb = p.get("dev")
-            if tb is not None:
-                meta = _decoder_meta(ctx, opt, model, et)
-                G, l = _cached_latents(ctx, meta, dec, d)
-                rows, cols, seg2, rel2, seg_ptr, seg_rel = tb.rows, tb.cols, tb.seg2, tb.rel2, tb.seg_ptr, tb.seg_rel
-                if fed:
-                    negs = torch.from_numpy(negs_host[et]).to(dev)
-            else:
-                G, l = _stacked_latents(ctx, dec, d)
-                # one upload: [rows | cols | (negatives) | seg_ptr | seg_ptr + n | seg_rel | seg_rel]
-                host = np.concatenate([p["rows"], p["cols"]] + ([negs_host[et]] if fed else []) +
-                                      [p["seg_ptr"], p["seg_ptr"][1:] + n, p["seg_rel"], p["seg_rel"]]).astype(np.int32)
-                buf = torch.from_numpy(host).to(dev)
-                rows, cols = buf[:n], buf[n:2 * n]
-                o = 3 * n if fed else 2 * n
-                seg2, o = buf[o:o + 2 * n_seg + 1], o + 2 * n_seg + 1
-                rel2 = buf[o:o + 2 * n_seg]
-                seg_ptr, seg_rel = seg2[:n_seg + 1], rel2[:n_seg]
-                if fed:
-                    negs = buf[2 * n:3 * n]
+            rec = _edge_type_record(ctx, opt, model, et)
+            G, l = _cached_latents(ctx, rec, dec, row_t.shape[1])
             t0 = _stage("operands", t0)
-            if not fed:
-                first = meta["first"] if tb is not None else first_relation(model, et)
+            if negs is None:
                 s = opt._sampler(ctx)
-                stack = _alias_stack(ctx, opt, et, first, K)
+                stack = _alias_stack(ctx, opt, et, rec["first"], model.edge_types[et])
                 if stack.shape[1] > row_t.shape[0]:
                     raise InvalidArgumentError("degrees list longer than the row embedding table")
                 nk = n // n_seg  # (equal batch sizes, and n > 0: every segment holds nk >= 1 pairs)
                 slot0 = -(-s.counter // nk)
-                tabs = stack.index_select(0, seg_rel.long()).contiguous()
+                tabs = stack.index_select(0, tb.seg_rel.long()).contiguous()
                 negs = kernels.unigram_sample_slots(tabs, slot0, nk, n, opt.seed, first_slot=slot0)
                 s.counter = (slot0 + n_seg) * nk
             t0 = _stage("sampler", t0)
             # positives, then negatives (the positive batch's columns: optimizer.py:51-57)
-            scores = kernels.decoder_score_seg(row_t, col_t, torch.cat([rows, negs]), torch.cat([cols, cols]), seg2,
-                                               G, l, seg_rel=rel2)
+            scores = kernels.decoder_score_seg(row_t, col_t, torch.cat([rows, negs]), torch.cat([cols, cols]), tb.seg2,
+                                               G, l, seg_rel=tb.rel2)
             pos, neg = scores[:n], scores[n:]
             costs.append(kernels.hinge_loss(pos, neg, opt.margin, workspace=kernels.hinge_workspace(dev)))
             t0 = _stage("score_hinge", t0)
-            gflat = dec_grads[et]
-            outs = {"dG": None, "dl": None, "dG_diag": None}
-            if tb is not None:  # the slices of gflat, from the cached offsets
-                for nm, (off, per) in meta["grad_slices"].items():
-                    outs[nm] = gflat[off:off + per * (d * d if nm == "dG" else d)]
-            else:
-                specs = [dec.latent(k) for k in range(K)]
-                gk, lk = specs[0][0], specs[0][2]
-
-                def stacked(c, per):  # the K variables' gradient slices as one [K, per] view of gflat
-                    off0 = (specs[0][c].tensor.data_ptr() - dec.flat.data_ptr()) // 4
-                    return gflat[off0:off0 + K * per]
-
-                if gk == "dense":
-                    shared = all(sp[1] is specs[0][1] for sp in specs)
-                    outs["dG"] = opt._grad_view(dec, gflat, specs[0][1]) if shared else stacked(1, d * d)
-                elif gk == "diag":
-                    outs["dG_diag"] = stacked(1, d)
-                if lk == "diag":
-                    outs["dl"] = stacked(3, d)
-            op = kernels.PreparedDecoderGradSeg(row_t, col_t, rows, cols, negs, seg_ptr, seg_rel, pos, neg, G, l,
-                                                opt.margin, **outs)
+            op = kernels.PreparedDecoderGradSeg(row_t, col_t, rows, cols, negs, tb.seg_ptr, tb.seg_rel, pos, neg, G, l,
+                                                opt.margin, **dec.layout.grad_outputs(dec_grads[et]))
             work.append((i, j, n, rows, cols, negs, op))
             t0 = _stage("gradient_setup", t0)
 

@@ -6,9 +6,9 @@ synthetic graph (config P: 1,932 relations), batch 512, device-drawn negatives.
                device time between events over --reps launches, --rounds rounds; the gather rate is
                the 8-byte edge pairs read plus the two 4-byte index arrays written, per second.
   (b) step     one trainall.train_step_all fed by EdgeBatches.batch (formed inside the timed pass)
-               against the same step fed by EdgeBatches.host_batch — the host-dict path, unchanged:
-               pack_batches, one upload per edge type, a walk over every decoder variable.  The host
-               dicts are built before the clock starts.
+               against the same step fed by EdgeBatches.host_batch — the host dicts: pack_batches and
+               one upload per edge type (trainall.type_batch) before the run, then the device-fed
+               step's path.  The host dicts are built before the clock starts.
   (c) stages   the device-fed step with a device synchronise after every stage (trainall.stage_log):
                batch formation, forward and plan, operands, sampler, scorer and hinge, gradient set-up,
                backward (decoder gradient, occurrence lists, row sums, GCN backward), update; the rest
@@ -155,8 +155,8 @@ def main():
     out.write_text(json.dumps(res) + "\n")
 
     # ---------------------------------------------------------------- (c) the stages of the device-fed step
-    # (the host-fed step's too: there "operands" holds the upload and the walk over the stacked latents,
-    # "gradient_setup" the walk over the variables, and pack_batches falls to the remainder)
+    # (the host-fed step's too: its stages are the device-fed step's; pack_batches and the upload precede the
+    # run and fall to the remainder)
     for kind in ("device_fed", "host_fed"):
         acc, totals, form = {}, [], []
         for r in range(a.rounds):

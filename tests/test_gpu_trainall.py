@@ -307,13 +307,8 @@ def test_all_relation_gradients_match_the_summed_oracle(golden_S, ref_all):
         assert np.array_equal(v, b) and np.array_equal(p.eval(), b)
 
 
-def test_accumulation_equals_the_per_relation_path(golden_S, ref_all):
-    """The same quantities against Σ opt.grads_vars over one Session.run per relation."""
-    from decagon_amd.trainall import train_step_all
-
-    batches, negs, cost_ref, _, _ = ref_all
-    dg, ph, model, opt, feed = _setup(golden_S)
-    sess = dg.Session()
+def _per_relation_sum(sess, ph, model, opt, feed, batches, negs):
+    """(Σ cost, Σ gradients in float64) of opt.grads_vars / opt.cost over one Session.run per relation."""
     total, cost_sum, e = None, 0.0, 0
     for (i, j), K in model.edge_types.items():
         for k in range(K):
@@ -325,9 +320,54 @@ def test_accumulation_equals_the_per_relation_path(golden_S, ref_all):
             g64 = [np.asarray(g, np.float64) for g, _ in gv]
             total = g64 if total is None else [a + b for a, b in zip(total, g64)]
             e += 1
+    return cost_sum, total
+
+
+def test_accumulation_equals_the_per_relation_path(golden_S, ref_all):
+    """The same quantities against Σ opt.grads_vars over one Session.run per relation."""
+    from decagon_amd.trainall import train_step_all
+
+    batches, negs, cost_ref, _, _ = ref_all
+    dg, ph, model, opt, feed = _setup(golden_S)
+    sess = dg.Session()
+    cost_sum, total = _per_relation_sum(sess, ph, model, opt, feed, batches, negs)
     cost, gv = train_step_all(sess, opt, ph, feed, batches, neg_samples=negs, apply=False)
     assert abs(cost - cost_sum) <= 1e-5 * abs(cost_sum)
     _assert_grads(gv, total)
+
+
+def test_decoders_whose_operands_are_no_views_take_the_one_path(golden_S, ref_all):
+    """DistMult on (1, 1) and InnerProduct on (0, 1) — the decoders whose (G, l) are expanded per
+    run, not views of the flat buffer — with the variables the model was constructed with:
+    (a) the step against the per-relation path, as above; (b) the step on an EdgeBatches' host
+    batches against the step on its device batches, bit for bit, twice in a row (the operands the
+    step keeps across runs, with nothing applied in between)."""
+    from decagon_amd import inits
+    from decagon_amd.trainall import train_step_all
+    from test_gpu_epochs import _edge_batches, _fed_negatives, _same
+
+    batches, negs, _, _, _ = ref_all
+    inits.set_random_seed(7)  # (the draws of the two decoders do not depend on the tests run before)
+    dg, ph, model, opt, feed = _setup(golden_S, decoders_override={(1, 1): "distmult", (0, 1): "innerproduct"})
+    kinds = {et: type(dec).__name__ for et, dec in model.edge_type2decoder.items()}
+    assert kinds[1, 1] == "DistMultDecoder" and kinds[0, 1] == "InnerProductDecoder"
+    sess = dg.Session()
+    cost_sum, total = _per_relation_sum(sess, ph, model, opt, feed, batches, negs)
+    cost, gv = train_step_all(sess, opt, ph, feed, batches, neg_samples=negs, apply=False)
+    assert abs(cost - cost_sum) <= 1e-5 * abs(cost_sum)
+    _assert_grads(gv, total)
+    names = list(model.vars)
+    dist = [q for q, nm in enumerate(names) if "relation_" in nm and model.vars[nm].tensor.dim() == 1]
+    assert len(dist) == model.edge_types[1, 1] and all(np.any(gv[q][0] != 0) for q in dist)
+
+    eb = _edge_batches(golden_S, model, opt, sess.device)
+    hb = eb.host_batch(0, 0)
+    assert (1, 1) in hb and (0, 1) in hb
+    fed = _fed_negatives(golden_S, hb, 5)
+    host = train_step_all(sess, opt, ph, feed, hb, neg_samples=fed, apply=False)
+    for _ in range(2):
+        _same(host, train_step_all(sess, opt, ph, feed, eb.batch(0, 0), neg_samples=fed, apply=False))
+    assert any(np.any(g != 0) for g, _ in host[1])
 
 
 def test_one_applied_step_is_tf_adam_and_shares_its_slots(golden_S, ref_all):
