@@ -275,8 +275,15 @@ SIGNATURES = {
     "dg_hinge_loss_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p]),
     "dg_hinge_loss_ws_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
     "dg_xent_loss_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p]),
+    "dg_xent_loss_ws_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
     "dg_decoder_grad_workspace": (c_int64, [c_int32, c_int32]),
     "dg_decoder_grad_f32": (
+        c_int32,
+        [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int64, c_void_p],
+    ),
+    "dg_decoder_grad_xent_f32": (
         c_int32,
         [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
          c_void_p, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -328,6 +335,12 @@ SIGNATURES = {
         [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
          c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32,
          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
+    ),
+    "dg_decoder_grad_seg_xent_f32": (
+        c_int32,
+        [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+         c_int32, c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32,
+         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p],
     ),
     "dg_segment_rows_sum_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p,
                                           c_int64, c_int32, c_void_p]),

@@ -372,19 +372,16 @@ __global__ __launch_bounds__(256) void hinge_kernel(const float* pos, const floa
     if (threadIdx.x == 0) loss[0] = s;
 }
 
-// Many-block hinge (config 5: 10^6 pairs): block b sums its contiguous chunk in a fixed
-// order, publishes the partial and takes a ticket; the last block adds the partials in block
-// order and resets the ticket (the decoder_hinge_kernel pattern) — deterministic for a given n.
-__global__ __launch_bounds__(256) void hinge_multi_kernel(const float* pos, const float* neg, int n,
-                                                          float margin, float* loss, float* partial,
-                                                          uint32_t* ticket) {
+// Many-block sum of a per-pair term (config 5: 10^6 pairs): block b sums its contiguous chunk in
+// a fixed order, publishes the partial and takes a ticket; the last block adds the partials in
+// block order and resets the ticket (the decoder_hinge_kernel pattern) — deterministic for a given n.
+template <typename F>
+__device__ __forceinline__ void multi_block_sum(int n, F term, float* loss, float* partial, uint32_t* ticket) {
     __shared__ int last;
     const int chunk = (n + (int)gridDim.x - 1) / (int)gridDim.x;
     const int p0 = blockIdx.x * chunk;
     const int cnt = max(0, min(n, p0 + chunk) - p0);
-    const float s = block_sum_256(cnt, [&](int q) {
-        return fmaxf(neg[p0 + q] - (pos[p0 + q] - margin), 0.f);
-    });
+    const float s = block_sum_256(cnt, [&](int q) { return term(p0 + q); });
     if (threadIdx.x == 0) {  // sc1 partial, drained, then the ticket (decoder_hinge_kernel)
         __hip_atomic_store(partial + blockIdx.x, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -399,6 +396,12 @@ __global__ __launch_bounds__(256) void hinge_multi_kernel(const float* pos, cons
         loss[0] = t;
         atomicExch(ticket, 0u);
     }
+}
+
+__global__ __launch_bounds__(256) void hinge_multi_kernel(const float* pos, const float* neg, int n,
+                                                          float margin, float* loss, float* partial,
+                                                          uint32_t* ticket) {
+    multi_block_sum(n, [&](int p) { return fmaxf(neg[p] - (pos[p] - margin), 0.f); }, loss, partial, ticket);
 }
 
 // log1p in double: the float log1pf's double-float arithmetic is vectorised by the compiler into
@@ -418,6 +421,31 @@ __global__ __launch_bounds__(256) void xent_kernel(const float* pos, const float
         return fmaxf(x, 0.f) + softplus_neg_abs(x);
     });
     if (threadIdx.x == 0) loss[0] = sp + w * sn;
+}
+
+// softplus(−|x|) = log(1 + e) with e = exp(−|x|) in (0, 1], in fp32: log(u) of the rounded u = 1 + e
+// plus the first-order term (e − (u − 1)) / u for what the rounding of u lost — within 2 ulp of
+// log1p(e) over the whole range, with plain single-precision instructions (no double-float log1pf:
+// see softplus_neg_abs).  e = 0 (|x| > 103.97) gives 0.
+__device__ __forceinline__ float softplus_neg_abs_f32(float x) {
+    const float e = expf(-fabsf(x));
+    const float u = 1.0f + e;
+    return logf(u) + (e - (u - 1.0f)) / u;
+}
+
+// The cross-entropy sum over many pairs (an all-relation step: 10^6 pairs), one term per pair:
+// sigmoid_cross_entropy_with_logits(z, x) = max(x,0) − x·z + log(1 + exp(−|x|)), z = 1 for pos, 0 for neg.
+__global__ __launch_bounds__(256) void xent_multi_kernel(const float* pos, const float* neg, int n, float w,
+                                                         float* loss, float* partial, uint32_t* ticket) {
+    multi_block_sum(
+        n,
+        [&](int p) {
+            const float x = pos[p], y = neg[p];
+            const float tp = fmaxf(x, 0.f) - x + softplus_neg_abs_f32(x);
+            const float tn = fmaxf(y, 0.f) + softplus_neg_abs_f32(y);
+            return tp + w * tn;
+        },
+        loss, partial, ticket);
 }
 
 __global__ __launch_bounds__(256) void unigram_sample_kernel(const uint2* table, int range, int n,
@@ -485,6 +513,17 @@ extern "C" int dg_xent_loss_f32(const float* pos, const float* neg, int32_t n, f
     if (n < 0 || !loss || (n > 0 && (!pos || !neg))) return DG_EINVAL;
     hipLaunchKernelGGL(xent_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        pos, neg, n, neg_weight, loss);
+    return dg::launch_status();
+}
+
+extern "C" int dg_xent_loss_ws_f32(const float* pos, const float* neg, int32_t n, float neg_weight, float* loss,
+                                   void* workspace, void* stream) {
+    if (n < 0 || !loss || !workspace || (n > 0 && (!pos || !neg))) return DG_EINVAL;
+    if (!dg::aligned16(workspace)) return DG_EALIGN;
+    const int blocks = max(1, min(DG_HINGE_WS_BLOCKS, dg::ceil_div(n, 4096)));
+    hipLaunchKernelGGL(xent_multi_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pos,
+                       neg, n, neg_weight, loss, reinterpret_cast<float*>(workspace) + 4,
+                       reinterpret_cast<uint32_t*>(workspace));
     return dg::launch_status();
 }
 

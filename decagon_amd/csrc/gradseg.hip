@@ -1,5 +1,6 @@
-// The decoder backward of the hinge cost for EVERY relation's batch of one edge type in one pass,
-// and the row reduction that turns per-pair gradient rows into the embeddings' gradient.
+// The decoder backward of the cost (hinge or sigmoid cross-entropy: loss_policy.h, whose a_p, b_p
+// are used below) for EVERY relation's batch of one edge type in one pass, and the row reduction
+// that turns per-pair gradient rows into the embeddings' gradient.
 //
 // Replaces (paths relative to the reference root):
 //   one tf.train.AdamOptimizer.minimize step per (relation, batch)   decagon/deep/optimizer.py:108-114,
@@ -12,12 +13,15 @@
 // the conventions of dg_decoder_score_seg_f32 (evalseg.hip) and dealt to waves in 32-pair tiles
 // by the virtual-tile map of segmap.h: no prefix sum, nothing read on the host.
 //
-//   pairs kernel   one wave per tile: a_p, then on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32)
-//                    mv[p]        = a_p · L·G·L·v_p            = ((V∘l)·Gᵀ)∘l
-//                    grad_cols[p] = a_p · L·Gᵀ·L·(un_p − u_p)  = ((D∘l)·G)∘l
-//                  G_k's fragments are loaded once per wave and serve the tile's 32 pairs.
-//   dM kernel      one wave per (segment, 32×32 tile of dM): dM_s = Σ_p a_p·(un_p − u_p)·v_pᵀ over
-//                  the segment's pairs in order (the contraction index of the MFMA chain).
+//   pairs kernel   one wave per tile: (a_p, b_p), then on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32)
+//                    mv[p]        = m_p · L·G·L·v_p                = ((V∘l)·Gᵀ)∘l
+//                    grad_cols[p] = L·Gᵀ·L·(b_p·un_p − a_p·u_p)    = ((D∘l)·G)∘l
+//                  G_k's fragments are loaded once per wave and serve the tile's 32 pairs.  Hinge:
+//                  m_p = a_p = b_p, the mask, so −mv[p] / +mv[p] are the two rows' gradients.  Xent:
+//                  m_p = 1 (mv stays one row per pair) and coef[p] = −a_p, coef[n_pairs + p] = +b_p
+//                  are stored beside it: the row reduction's `sign` carries the weights.
+//   dM kernel      one wave per (segment, 32×32 tile of dM): dM_s = Σ_p (b_p·un_p − a_p·u_p)·v_pᵀ
+//                  over the segment's pairs in order (the contraction index of the MFMA chain).
 //   vars kernel    dG / dG_diag / dl of every segment's relation from dM_s; and, for a shared G,
 //   shared-G sum   dG = Σ_s L_k·dM_s·L_k over 16 contiguous slices of the segment list, each in
 //                  segment order, the slices' sums added in slice order.
@@ -26,6 +30,7 @@
 // one workgroup per output row, the list split over the waves in fixed chunks and the waves'
 // sums combined in a fixed tree.  No float atomics anywhere: results are bitwise reproducible.
 #include "common.h"
+#include "loss_policy.h"
 #include "rel_operands.h"
 #include "segmap.h"
 
@@ -46,33 +51,37 @@ struct GradSegArgs {
     dg::RelOps ops;
     float* mv;
     float* grad_cols;
-    float* dM;  // [n_seg][d][d]
+    float* coef;  // [2·n_pairs] (policies with kCoef)
+    float* dM;    // [n_seg][d][d]
     float* dG;
     float* dl;
     float* dG_diag;
     int64_t ld_row, ld_col;
     int32_t n_rows, n_cols, n_seg, n_pairs, n_tiles;
-    float margin;
+    float param;  // the cost's parameter: margin (hinge), neg_weight (xent)
     int32_t pad;
 };
 
-// Pair p's indices and hinge mask: act = inside the tables and neg − (pos − margin) > 0.  An
-// inactive pair gets index 0 everywhere (a row that exists: loads stay unconditional).
-__device__ __forceinline__ bool pair_meta(const GradSegArgs& a, int p, bool in_seg, int& r, int& c, int& rn) {
+// Pair p's indices and the cost's coefficients (hinge: the mask, inside the tables and
+// neg − (pos − margin) > 0; a pair outside the tables has none).  A pair that is not live gets
+// index 0 everywhere (a row that exists: loads stay unconditional).
+template <class Loss>
+__device__ __forceinline__ typename Loss::Coef pair_meta(const GradSegArgs& a, int p, bool in_seg, int& r, int& c,
+                                                         int& rn) {
     r = in_seg ? a.rows[p] : 0;
     c = in_seg ? a.cols[p] : 0;
     rn = in_seg ? a.negs[p] : 0;
-    const float z = in_seg ? a.neg[p] - (a.pos[p] - a.margin) : 0.f;
     const bool ok = in_seg && r >= 0 && r < a.n_rows && rn >= 0 && rn < a.n_rows && c >= 0 && c < a.n_cols;
-    const bool act = ok && z > 0.f;
-    if (!act) r = c = rn = 0;
-    return act;
+    const typename Loss::Coef cf =
+        in_seg ? Loss::coef(a.pos[p], a.neg[p], a.param, ok) : Loss::coef(0.f, 0.f, 0.f, false);
+    if (!Loss::live(cf)) r = c = rn = 0;
+    return cf;
 }
 
 // One wave per 32-pair tile.  MFMA step j of a k-chunk takes k = (kD/2)·h + j from lane half h
 // (the contraction order is free), so a lane's A operands are kD/2 contiguous floats of its
 // pair's rows (float4 loads) and its Gᵀ fragment kD/2 contiguous floats of one row of G.
-template <int kD>
+template <int kD, class Loss>
 __global__ __launch_bounds__(256) void grad_seg_pairs_kernel(const GradSegArgs a) {
     constexpr int kH = kD / 2;
     const int lane = threadIdx.x & 63;
@@ -94,7 +103,14 @@ __global__ __launch_bounds__(256) void grad_seg_pairs_kernel(const GradSegArgs a
     const int i = lane & 31;
     const int h = lane >> 5;
     int r, c, rn;
-    const bool act = pair_meta(a, p0 + i, rel_ok && p0 + i < end, r, c, rn);
+    const typename Loss::Coef cf = pair_meta<Loss>(a, p0 + i, rel_ok && p0 + i < end, r, c, rn);
+    const bool act = Loss::live(cf);
+    if constexpr (Loss::kCoef) {
+        if (h == 0 && p0 + i < end) {
+            a.coef[p0 + i] = -Loss::a(cf);
+            a.coef[(int64_t)a.n_pairs + p0 + i] = Loss::b(cf);
+        }
+    }
     const float4* u4 = reinterpret_cast<const float4*>(a.row_table + (int64_t)r * a.ld_row + kH * h);
     const float4* un4 = reinterpret_cast<const float4*>(a.row_table + (int64_t)rn * a.ld_row + kH * h);
     const float4* v4 = reinterpret_cast<const float4*>(a.col_table + (int64_t)c * a.ld_col + kH * h);
@@ -108,10 +124,10 @@ __global__ __launch_bounds__(256) void grad_seg_pairs_kernel(const GradSegArgs a
         xv[4 * j4 + 1] = act ? vv.y * ll.y : 0.f;
         xv[4 * j4 + 2] = act ? vv.z * ll.z : 0.f;
         xv[4 * j4 + 3] = act ? vv.w * ll.w : 0.f;
-        xd[4 * j4] = act ? (nn.x - uu.x) * ll.x : 0.f;
-        xd[4 * j4 + 1] = act ? (nn.y - uu.y) * ll.y : 0.f;
-        xd[4 * j4 + 2] = act ? (nn.z - uu.z) * ll.z : 0.f;
-        xd[4 * j4 + 3] = act ? (nn.w - uu.w) * ll.w : 0.f;
+        xd[4 * j4] = act ? Loss::diff(cf, nn.x, uu.x) * ll.x : 0.f;
+        xd[4 * j4 + 1] = act ? Loss::diff(cf, nn.y, uu.y) * ll.y : 0.f;
+        xd[4 * j4 + 2] = act ? Loss::diff(cf, nn.z, uu.z) * ll.z : 0.f;
+        xd[4 * j4 + 3] = act ? Loss::diff(cf, nn.w, uu.w) * ll.w : 0.f;
     }
 #pragma unroll 1
     for (int n0 = 0; n0 < kD; n0 += 32) {
@@ -144,7 +160,7 @@ __global__ __launch_bounds__(256) void grad_seg_pairs_kernel(const GradSegArgs a
 // One wave per (segment, 32×32 tile (ta, tb) of dM): the segment's pairs in chunks of 32, MFMA
 // step s2 of a chunk taking pair 2·s2 + h from lane half h — pairs in order.  Lane j < 32 (both
 // halves) reads chunk pair j's indices and mask once; the steps fetch them by shuffle.
-template <int kD>
+template <int kD, class Loss>
 __global__ __launch_bounds__(256) void grad_seg_dm_kernel(const GradSegArgs a) {
     constexpr int kT = kD / 32;
     const int lane = threadIdx.x & 63;
@@ -162,22 +178,24 @@ __global__ __launch_bounds__(256) void grad_seg_dm_kernel(const GradSegArgs a) {
 #pragma unroll 1
         for (int c0 = beg; c0 < end; c0 += 32) {
             int r, c, rn;
-            const bool act = pair_meta(a, c0 + i, c0 + i < end, r, c, rn);
+            const typename Loss::Coef cf = pair_meta<Loss>(a, c0 + i, c0 + i < end, r, c, rn);
             float un[16], uu[16], vv[16];
-            bool on[16];
+            typename Loss::Coef on[16];
 #pragma unroll
             for (int s2 = 0; s2 < 16; ++s2) {
                 const int src = 2 * s2 + h;
                 const int rr = __shfl(r, src), cc = __shfl(c, src), nn = __shfl(rn, src);
-                on[s2] = __shfl((int)act, src) != 0;
+                on[s2] = Loss::shfl(cf, src);
                 uu[s2] = a.row_table[(int64_t)rr * a.ld_row + ta * 32 + i];
                 un[s2] = a.row_table[(int64_t)nn * a.ld_row + ta * 32 + i];
                 vv[s2] = a.col_table[(int64_t)cc * a.ld_col + tb * 32 + i];
             }
 #pragma unroll
-            for (int s2 = 0; s2 < 16; ++s2)
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(on[s2] ? un[s2] - uu[s2] : 0.f, on[s2] ? vv[s2] : 0.f, acc,
-                                                           0, 0, 0);
+            for (int s2 = 0; s2 < 16; ++s2) {
+                const bool lv = Loss::live(on[s2]);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(lv ? Loss::diff(on[s2], un[s2], uu[s2]) : 0.f,
+                                                           lv ? vv[s2] : 0.f, acc, 0, 0, 0);
+            }
         }
     }
     float* out = a.dM + (int64_t)s * kD * kD;
@@ -355,17 +373,20 @@ extern "C" int64_t dg_decoder_grad_seg_workspace(int32_t n_seg, int32_t d) {
     return 4LL * n_seg * d * d;
 }
 
-extern "C" int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, int32_t n_rows,
-                                       const float* col_table, int64_t ld_col, int32_t n_cols,
-                                       const int32_t* rows, const int32_t* cols, const int32_t* neg_rows,
-                                       const int32_t* seg_ptr, const int32_t* seg_rel, int32_t n_seg,
-                                       int32_t n_pairs, const float* pos, const float* neg, float margin,
-                                       const float* G, int64_t g_stride, const float* l, int64_t l_stride,
-                                       int32_t n_rel, int32_t d, float* mv, float* grad_cols, float* dG, float* dl,
-                                       float* dG_diag, void* workspace, int64_t workspace_bytes, void* stream) {
+// dg_decoder_grad_seg_f32 / dg_decoder_grad_seg_xent_f32: the same launches, the pair and dM kernels
+// of the cost (coef: the xent form's output, NULL for the hinge).
+template <class Loss>
+static int grad_seg_launch(const float* row_table, int64_t ld_row, int32_t n_rows, const float* col_table,
+                           int64_t ld_col, int32_t n_cols, const int32_t* rows, const int32_t* cols,
+                           const int32_t* neg_rows, const int32_t* seg_ptr, const int32_t* seg_rel, int32_t n_seg,
+                           int32_t n_pairs, const float* pos, const float* neg, float param, const float* G,
+                           int64_t g_stride, const float* l, int64_t l_stride, int32_t n_rel, int32_t d, float* mv,
+                           float* grad_cols, float* coef, float* dG, float* dl, float* dG_diag, void* workspace,
+                           int64_t workspace_bytes, void* stream) {
     if (n_seg <= 0 || n_pairs < 0 || (d != 32 && d != 64)) return DG_EINVAL;
     if (!row_table || !col_table || !seg_ptr || !G) return DG_EINVAL;
     if (n_pairs > 0 && (!rows || !cols || !neg_rows || !pos || !neg || !mv || !grad_cols)) return DG_EINVAL;
+    if (Loss::kCoef && n_pairs > 0 && !coef) return DG_EINVAL;
     if (n_rows < 1 || n_cols < 1 || ld_row < d || ld_col < d) return DG_EINVAL;
     GradSegArgs a{};
     if (dg::rel_ops(G, g_stride, l, l_stride, n_rel, d, seg_rel != nullptr, n_seg, a.ops) != DG_OK) return DG_EINVAL;
@@ -390,6 +411,7 @@ extern "C" int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, i
     a.neg = neg;
     a.mv = mv;
     a.grad_cols = grad_cols;
+    a.coef = coef;
     a.dM = static_cast<float*>(workspace);
     a.dG = dG;
     a.dl = dl;
@@ -401,20 +423,20 @@ extern "C" int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, i
     a.n_seg = n_seg;
     a.n_pairs = n_pairs;
     a.n_tiles = (int32_t)dg::seg_tile_grid(n_pairs, n_seg, 32);
-    a.margin = margin;
+    a.param = param;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(dg::ceil_div(a.n_tiles, 4)), block(256);
     if (d == 32)
-        hipLaunchKernelGGL(grad_seg_pairs_kernel<32>, grid, block, 0, st, a);
+        hipLaunchKernelGGL((grad_seg_pairs_kernel<32, Loss>), grid, block, 0, st, a);
     else
-        hipLaunchKernelGGL(grad_seg_pairs_kernel<64>, grid, block, 0, st, a);
+        hipLaunchKernelGGL((grad_seg_pairs_kernel<64, Loss>), grid, block, 0, st, a);
     if (!vars) return dg::launch_status();
     const int tiles = d / 32;
     const dim3 dgrid(dg::ceil_div((int64_t)n_seg * tiles * tiles, 4));
     if (d == 32)
-        hipLaunchKernelGGL(grad_seg_dm_kernel<32>, dgrid, block, 0, st, a);
+        hipLaunchKernelGGL((grad_seg_dm_kernel<32, Loss>), dgrid, block, 0, st, a);
     else
-        hipLaunchKernelGGL(grad_seg_dm_kernel<64>, dgrid, block, 0, st, a);
+        hipLaunchKernelGGL((grad_seg_dm_kernel<64, Loss>), dgrid, block, 0, st, a);
     const bool per_rel_dG = dG && g_stride != 0;
     if (per_rel_dG || dl || dG_diag) {
         const int eb = per_rel_dG ? dg::ceil_div((int64_t)d * d, 256) : 1;
@@ -423,6 +445,35 @@ extern "C" int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, i
     if (dG && g_stride == 0)
         hipLaunchKernelGGL(grad_seg_shared_dg_kernel, dim3(d * d / 64), dim3(64 * kSumSlices), 0, st, a, d);
     return dg::launch_status();
+}
+
+extern "C" int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, int32_t n_rows,
+                                       const float* col_table, int64_t ld_col, int32_t n_cols,
+                                       const int32_t* rows, const int32_t* cols, const int32_t* neg_rows,
+                                       const int32_t* seg_ptr, const int32_t* seg_rel, int32_t n_seg,
+                                       int32_t n_pairs, const float* pos, const float* neg, float margin,
+                                       const float* G, int64_t g_stride, const float* l, int64_t l_stride,
+                                       int32_t n_rel, int32_t d, float* mv, float* grad_cols, float* dG, float* dl,
+                                       float* dG_diag, void* workspace, int64_t workspace_bytes, void* stream) {
+    return grad_seg_launch<dg::HingeLoss>(row_table, ld_row, n_rows, col_table, ld_col, n_cols, rows, cols, neg_rows,
+                                          seg_ptr, seg_rel, n_seg, n_pairs, pos, neg, margin, G, g_stride, l, l_stride,
+                                          n_rel, d, mv, grad_cols, nullptr, dG, dl, dG_diag, workspace,
+                                          workspace_bytes, stream);
+}
+
+extern "C" int dg_decoder_grad_seg_xent_f32(const float* row_table, int64_t ld_row, int32_t n_rows,
+                                            const float* col_table, int64_t ld_col, int32_t n_cols,
+                                            const int32_t* rows, const int32_t* cols, const int32_t* neg_rows,
+                                            const int32_t* seg_ptr, const int32_t* seg_rel, int32_t n_seg,
+                                            int32_t n_pairs, const float* pos, const float* neg, float neg_weight,
+                                            const float* G, int64_t g_stride, const float* l, int64_t l_stride,
+                                            int32_t n_rel, int32_t d, float* mv, float* grad_cols, float* coef,
+                                            float* dG, float* dl, float* dG_diag, void* workspace,
+                                            int64_t workspace_bytes, void* stream) {
+    return grad_seg_launch<dg::XentLoss>(row_table, ld_row, n_rows, col_table, ld_col, n_cols, rows, cols, neg_rows,
+                                         seg_ptr, seg_rel, n_seg, n_pairs, pos, neg, neg_weight, G, g_stride, l,
+                                         l_stride, n_rel, d, mv, grad_cols, coef, dG, dl, dG_diag, workspace,
+                                         workspace_bytes, stream);
 }
 
 extern "C" int32_t dg_segment_rows_sum_chunk(void) { return kRowChunk; }

@@ -1,9 +1,10 @@
-// Training-step kernels for gfx950 (MI355X): the backward of the hinge cost through the
-// edge decoder and the row L2 normalisation, and TF 1.8's Adam update.
+// Training-step kernels for gfx950 (MI355X): the backward of the cost (hinge or sigmoid
+// cross-entropy: loss_policy.h) through the edge decoder and the row L2 normalisation, and TF 1.8's Adam update.
 //
 // Replaces (paths relative to the reference root):
 //   tf.train.AdamOptimizer(lr).minimize(cost)            decagon/deep/optimizer.py:108-114
 //     - the gradient of DecagonOptimizer._hinge_loss      optimizer.py:116-120
+//       or of DecagonOptimizer._xent_loss                 optimizer.py:122-127
 //       through batch_predict's u·L·G·L·v                 optimizer.py:51-57, :63-85
 //       and the gathers from the embeddings               optimizer.py:66-76
 //     - the gradient of tf.nn.l2_normalize(dim=1)         layers.py:93, :117
@@ -14,6 +15,7 @@
 //
 // Sums run in a fixed order (no float atomics): results are bitwise reproducible.
 #include "common.h"
+#include "loss_policy.h"
 
 namespace {
 
@@ -22,13 +24,13 @@ using dg::f32x16;
 constexpr int kPairChunk = 64;   // pairs per dM partial
 
 // ---------------------------------------------------------------- decoder, per pair
-// One wave per pair p.  With a_p = [neg_p - (pos_p - margin) > 0] (relu's gradient mask)
-// the cost's gradient w.r.t. the positive score is -a_p and w.r.t. the negative one +a_p,
-// and with M = L·G·L (L = diag(l)):
+// One wave per pair p.  The cost's gradient w.r.t. the positive score is -a_p and w.r.t. the
+// negative one +b_p (loss_policy.h; the hinge: a_p = b_p = [neg_p - (pos_p - margin) > 0], relu's
+// gradient mask), and with M = L·G·L (L = diag(l)):
 //   grad_rows[p]     = -a_p · M·v_p          (the positive row u_p)
-//   grad_rows[n + p] = +a_p · M·v_p          (the negative row un_p)
-//   grad_cols[p]     =  a_p · Mᵀ·(un_p - u_p)
-//   xw[p] = a_p·(un_p - u_p),  vw[p] = v_p   (operands of dM = Σ_p xw[p]·vw[p]ᵀ)
+//   grad_rows[n + p] = +b_p · M·v_p          (the negative row un_p)
+//   grad_cols[p]     =  Mᵀ·(b_p·un_p - a_p·u_p)
+//   xw[p] = b_p·un_p - a_p·u_p,  vw[p] = v_p   (operands of dM = Σ_p xw[p]·vw[p]ᵀ)
 struct PairArgs {
     const float* row_table;
     const float* col_table;
@@ -47,10 +49,11 @@ struct PairArgs {
     int64_t ld_col;
     int32_t n;
     int32_t d;
-    float margin;
+    float param;  // the cost's parameter: margin (hinge), neg_weight (xent)
     int32_t pad;
 };
 
+template <class Loss>
 __global__ __launch_bounds__(256) void decoder_grad_pairs_kernel(const PairArgs a) {
     __shared__ float lv_s[4][256];
     __shared__ float dd_s[4][256];
@@ -59,15 +62,15 @@ __global__ __launch_bounds__(256) void decoder_grad_pairs_kernel(const PairArgs 
     const int p = blockIdx.x * 4 + w;
     if (p >= a.n) return;  // wave-uniform; no block barriers below
     const int d = a.d;
-    const float z = a.neg[p] - (a.pos[p] - a.margin);
-    const bool act = z > 0.f;
+    const typename Loss::Coef cf = Loss::coef(a.pos[p], a.neg[p], a.param, true);
+    const bool act = Loss::live(cf);
     const float* u = a.row_table + (int64_t)a.rows[p] * a.ld_row;
     const float* un = a.row_table + (int64_t)a.negs[p] * a.ld_row;
     const float* v = a.col_table + (int64_t)a.cols[p] * a.ld_col;
     for (int c = lane; c < d; c += 64) {
         const float lc = a.l ? a.l[c] : 1.0f;
         const float vc = v[c];
-        const float dc = act ? un[c] - u[c] : 0.f;
+        const float dc = act ? Loss::diff(cf, un[c], u[c]) : 0.f;
         lv_s[w][c] = lc * vc;
         dd_s[w][c] = lc * dc;
         a.xw[(int64_t)p * d + c] = dc;
@@ -87,8 +90,8 @@ __global__ __launch_bounds__(256) void decoder_grad_pairs_kernel(const PairArgs 
             mv *= lc;
             mtd *= lc;
         }
-        a.grad_rows[(int64_t)p * d + c] = act ? -mv : 0.f;
-        a.grad_rows[((int64_t)a.n + p) * d + c] = act ? mv : 0.f;
+        a.grad_rows[(int64_t)p * d + c] = act ? Loss::pos_row(cf, mv) : 0.f;
+        a.grad_rows[((int64_t)a.n + p) * d + c] = act ? Loss::neg_row(cf, mv) : 0.f;
         a.grad_cols[(int64_t)p * d + c] = mtd;
     }
 }
@@ -366,12 +369,13 @@ extern "C" int64_t dg_decoder_grad_workspace(int32_t n, int32_t d) {
     return 4 * (2 * (int64_t)n * d + nch * d * d + (int64_t)d * d);
 }
 
-extern "C" int dg_decoder_grad_f32(const float* row_table, int64_t ld_row, const float* col_table,
-                                   int64_t ld_col, const int32_t* rows, const int32_t* cols,
-                                   const int32_t* neg_rows, int32_t n, const float* pos, const float* neg,
-                                   const float* G, const float* l, int32_t d, float margin,
-                                   float* grad_rows, float* grad_cols, float* dG, float* dl,
-                                   float* dG_diag, void* workspace, int64_t workspace_bytes, void* stream) {
+// dg_decoder_grad_f32 / dg_decoder_grad_xent_f32: the same launches, the pair kernel of the cost.
+template <class Loss>
+static int decoder_grad_launch(const float* row_table, int64_t ld_row, const float* col_table, int64_t ld_col,
+                        const int32_t* rows, const int32_t* cols, const int32_t* neg_rows, int32_t n,
+                        const float* pos, const float* neg, const float* G, const float* l, int32_t d, float param,
+                        float* grad_rows, float* grad_cols, float* dG, float* dl, float* dG_diag, void* workspace,
+                        int64_t workspace_bytes, void* stream) {
     if (n < 0 || d < 32 || d > 256 || (d & 31)) return DG_EINVAL;
     if (n == 0) return DG_OK;
     if (!row_table || !col_table || !rows || !cols || !neg_rows || !pos || !neg || !G || !grad_rows ||
@@ -387,8 +391,8 @@ extern "C" int dg_decoder_grad_f32(const float* row_table, int64_t ld_row, const
     float* dM = part + (int64_t)nch * d * d;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     PairArgs pa{row_table, col_table, rows, cols, neg_rows, pos, neg, G, l, grad_rows, grad_cols, xw, vw,
-                ld_row, ld_col, n, d, margin, 0};
-    hipLaunchKernelGGL(decoder_grad_pairs_kernel, dim3(dg::ceil_div(n, 4)), dim3(256), 0, st, pa);
+                ld_row, ld_col, n, d, param, 0};
+    hipLaunchKernelGGL(decoder_grad_pairs_kernel<Loss>, dim3(dg::ceil_div(n, 4)), dim3(256), 0, st, pa);
     if (!dG && !dl && !dG_diag) return dg::launch_status();
     const int tiles = d / 32;
     hipLaunchKernelGGL(decoder_grad_dm_kernel, dim3(dg::ceil_div((int64_t)tiles * tiles * nch, 4)), dim3(256), 0,
@@ -398,6 +402,28 @@ extern "C" int dg_decoder_grad_f32(const float* row_table, int64_t ld_row, const
     if (dl || dG_diag)
         hipLaunchKernelGGL(decoder_grad_vec_kernel, dim3(1), dim3(256), 0, st, dM, G, l, d, dl, dG_diag);
     return dg::launch_status();
+}
+
+extern "C" int dg_decoder_grad_f32(const float* row_table, int64_t ld_row, const float* col_table,
+                                   int64_t ld_col, const int32_t* rows, const int32_t* cols,
+                                   const int32_t* neg_rows, int32_t n, const float* pos, const float* neg,
+                                   const float* G, const float* l, int32_t d, float margin,
+                                   float* grad_rows, float* grad_cols, float* dG, float* dl,
+                                   float* dG_diag, void* workspace, int64_t workspace_bytes, void* stream) {
+    return decoder_grad_launch<dg::HingeLoss>(row_table, ld_row, col_table, ld_col, rows, cols, neg_rows, n, pos, neg,
+                                              G, l, d, margin, grad_rows, grad_cols, dG, dl, dG_diag, workspace,
+                                              workspace_bytes, stream);
+}
+
+extern "C" int dg_decoder_grad_xent_f32(const float* row_table, int64_t ld_row, const float* col_table,
+                                        int64_t ld_col, const int32_t* rows, const int32_t* cols,
+                                        const int32_t* neg_rows, int32_t n, const float* pos, const float* neg,
+                                        const float* G, const float* l, int32_t d, float neg_weight,
+                                        float* grad_rows, float* grad_cols, float* dG, float* dl,
+                                        float* dG_diag, void* workspace, int64_t workspace_bytes, void* stream) {
+    return decoder_grad_launch<dg::XentLoss>(row_table, ld_row, col_table, ld_col, rows, cols, neg_rows, n, pos, neg,
+                                             G, l, d, neg_weight, grad_rows, grad_cols, dG, dl, dG_diag, workspace,
+                                             workspace_bytes, stream);
 }
 
 extern "C" int dg_scatter_rows_f32(const int32_t* idx, int32_t n, const float* src, int32_t d, float* out,

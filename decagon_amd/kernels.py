@@ -1579,16 +1579,36 @@ def hinge_workspace(device) -> torch.Tensor:
 
 
 def xent_loss(pos: torch.Tensor, neg: torch.Tensor, neg_weight: float,
-              out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+              out: Optional[torch.Tensor] = None, stream=None,
+              workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Σ softplus(−pos) + neg_weight·Σ softplus(neg) (optimizer.py:122-127): one workgroup, or — with
+    a workspace as hinge_loss takes it (hinge_workspace() serves both) — up to 256, in fp32 terms."""
     _dev(pos, torch.float32, "pos")
     _dev(neg, torch.float32, "neg")
     if pos.numel() != neg.numel():
         raise ValueError("pos/neg length mismatch")
     if out is None:
         out = torch.empty(1, device=pos.device, dtype=torch.float32)
+    if workspace is not None:
+        if workspace.numel() * workspace.element_size() < _lib.DG_HINGE_WS_BYTES or not workspace.is_cuda:
+            raise ValueError("xent workspace too small")
+        check(_lib.load().dg_xent_loss_ws_f32(pos.data_ptr(), neg.data_ptr(), pos.numel(), float(neg_weight),
+                                               out.data_ptr(), workspace.data_ptr(), _stream_ptr(stream)),
+              "dg_xent_loss_ws_f32")
+        return out
     check(_lib.load().dg_xent_loss_f32(pos.data_ptr(), neg.data_ptr(), pos.numel(), float(neg_weight),
                                         out.data_ptr(), _stream_ptr(stream)), "dg_xent_loss_f32")
     return out
+
+
+LOSSES = ("hinge", "xent")  # the costs of optimizer.py:116-127 the backward kernels know
+
+
+def loss_param(loss: str, margin: float, neg_weight: float) -> float:
+    """The one parameter of the cost's kernels: the hinge's margin, the cross-entropy's neg_weight."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+    return float(margin) if loss == "hinge" else float(neg_weight)
 
 
 def unigram_sample(table: torch.Tensor, n: int, seed: int, offset: int,
@@ -1885,11 +1905,13 @@ class PreparedDecoderHinge:
 class PreparedDecoderGrad:
     """dg_decoder_grad_f32 for one batch: row / column gradient rows of the n positive and n
     negative pairs, and the decoder parameter gradients dG = L·dM·L, dl, diag(dG) (each
-    written only if its output tensor is given)."""
+    written only if its output tensor is given).  loss="xent": dg_decoder_grad_xent_f32, the
+    same outputs for the cross-entropy cost with `neg_weight` (margin is then unused)."""
 
     def __init__(self, row_table, col_table, rows, cols, neg_rows, pos, neg, G, l, margin: float,
                  dG: Optional[torch.Tensor] = None, dl: Optional[torch.Tensor] = None,
-                 dG_diag: Optional[torch.Tensor] = None):
+                 dG_diag: Optional[torch.Tensor] = None, loss: str = "hinge", neg_weight: float = 1.0):
+        param = loss_param(loss, margin, neg_weight)
         for t, nm, dt in ((row_table, "row_table", torch.float32), (col_table, "col_table", torch.float32),
                           (rows, "rows", torch.int32), (cols, "cols", torch.int32),
                           (neg_rows, "neg_rows", torch.int32), (pos, "pos", torch.float32),
@@ -1922,12 +1944,13 @@ class PreparedDecoderGrad:
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         self._args = [row_table.data_ptr(), row_table.shape[1], col_table.data_ptr(), col_table.shape[1],
                       rows.data_ptr(), cols.data_ptr(), neg_rows.data_ptr(), n, pos.data_ptr(), neg.data_ptr(),
-                      G.data_ptr(), ptr(l), d, float(margin), self.grad_rows.data_ptr(),
+                      G.data_ptr(), ptr(l), d, param, self.grad_rows.data_ptr(),
                       self.grad_cols.data_ptr(), ptr(dG), ptr(dl), ptr(dG_diag), self._ws.data_ptr(), nbytes]
-        self._fn = lib.dg_decoder_grad_f32
+        self._name = "dg_decoder_grad_f32" if loss == "hinge" else "dg_decoder_grad_xent_f32"
+        self._fn = getattr(lib, self._name)
 
     def __call__(self, stream=None) -> None:
-        check(self._fn(*self._args, _stream_ptr(stream)), "dg_decoder_grad_f32")
+        check(self._fn(*self._args, _stream_ptr(stream)), self._name)
         n = self._rows.numel()  # the scatter's row index list (negatives may be resampled per step)
         self.row_idx[:n].copy_(self._rows)
         self.row_idx[n:].copy_(self._negs)
@@ -1956,11 +1979,17 @@ class PreparedDecoderGradSeg:
     distinct; outputs of relations without a segment are left untouched.
 
     G: [d, d] or [K, d, d]; l: None, [d] or [K, d]; seg_ptr device int32 [n_seg + 1], never read
-    on the host."""
+    on the host.
+
+    loss="xent": dg_decoder_grad_seg_xent_f32 for the cross-entropy cost with `neg_weight` (margin is
+    then unused).  `mv[p]` = M_k·v_p is then unweighted and `.coef` [2n] holds the weights of the
+    two rows it serves: coef[p] = −σ(−pos_p) for the positive row, coef[n + p] = +neg_weight·σ(neg_p)
+    for the negative one (segment_rows_sum's `sign`).  With the hinge there is no `.coef`."""
 
     def __init__(self, row_table, col_table, rows, cols, neg_rows, seg_ptr, seg_rel, pos, neg, G, l,
                  margin: float, dG: Optional[torch.Tensor] = None, dl: Optional[torch.Tensor] = None,
-                 dG_diag: Optional[torch.Tensor] = None):
+                 dG_diag: Optional[torch.Tensor] = None, loss: str = "hinge", neg_weight: float = 1.0):
+        param = loss_param(loss, margin, neg_weight)
         idx = [(rows, "rows"), (cols, "cols"), (neg_rows, "neg_rows"), (seg_ptr, "seg_ptr"), (seg_rel, "seg_rel")]
         outs = [(pos, "pos"), (neg, "neg"), (dG, "dG"), (dl, "dl"), (dG_diag, "dG_diag")]
         ops = RelOperands.build("decoder_grad_seg", row_table, col_table, G, l, WIDTHS_MFMA, idx)
@@ -1996,16 +2025,21 @@ class PreparedDecoderGradSeg:
         self._ws = torch.empty(max(1, nbytes // 4), device=dev) if vars_ else None
         self._keep = (row_table, col_table, rows, cols, neg_rows, seg_ptr, seg_rel, pos, neg, G, l, dG, dl, dG_diag)
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._name = "dg_decoder_grad_seg_f32"
+        coef = []
+        if loss == "xent":  # (zeros: pairs outside every segment are not written, and weigh nothing)
+            self.coef = torch.zeros(2 * n, device=dev)
+            self._name, coef = "dg_decoder_grad_seg_xent_f32", [ptr(self.coef) if n else None]
         self._args = [row_table.data_ptr(), d, ops.n_rows, col_table.data_ptr(), d, ops.n_cols,
                       ptr(rows) if n else None, ptr(cols) if n else None, ptr(neg_rows) if n else None,
                       seg_ptr.data_ptr(), ptr(seg_rel), n_seg, n, ptr(pos) if n else None, ptr(neg) if n else None,
-                      float(margin), *ops.c_args(), ops.n_rel(n_seg, seg_rel is not None), d,
-                      ptr(self.mv) if n else None, ptr(self.grad_cols) if n else None, ptr(dG), ptr(dl),
+                      param, *ops.c_args(), ops.n_rel(n_seg, seg_rel is not None), d,
+                      ptr(self.mv) if n else None, ptr(self.grad_cols) if n else None, *coef, ptr(dG), ptr(dl),
                       ptr(dG_diag), ptr(self._ws), nbytes if vars_ else 0]
-        self._fn = lib.dg_decoder_grad_seg_f32
+        self._fn = getattr(lib, self._name)
 
     def __call__(self, stream=None) -> None:
-        check(self._fn(*self._args, _stream_ptr(stream)), "dg_decoder_grad_seg_f32")
+        check(self._fn(*self._args, _stream_ptr(stream)), self._name)
 
 
 def segment_rows_chunk() -> Tuple[int, int]:

@@ -10,8 +10,13 @@ tf.nn.fixed_unigram_candidate_sampler (:37-49); feeding `opt.neg_samples` inject
 (TF semantics: any tensor may be fed), which is how parity tests pin them.
 
 `opt_op` (:108-114) runs the training step on the device: the forward in training mode, the
-backward of the hinge cost (decagon_amd/train.py) and TF 1.8's Adam on every variable.
+backward of the cost (decagon_amd/train.py) and TF 1.8's Adam on every variable.
 `grads_vars` returns (gradient, value) pairs of every variable, like compute_gradients.
+
+The cost is the reference's `_hinge_loss` (:116-120, the one it builds) or, with `loss="xent"`,
+its `_xent_loss` (:122-127): Σ softplus(−pos) + neg_sample_weights·Σ softplus(neg).  The switch
+reaches `cost`, `opt_op`, `grads_vars` and trainall.train_step_all; scores and negatives are the
+same launch either way.
 """
 from __future__ import annotations
 
@@ -35,7 +40,11 @@ class _Sampler:
 
 class DecagonOptimizer:
     def __init__(self, embeddings, latent_inters, latent_varies, degrees, edge_types,
-                 edge_type2dim, placeholders, margin=0.1, neg_sample_weights=1., batch_size=100):
+                 edge_type2dim, placeholders, margin=0.1, neg_sample_weights=1., batch_size=100,
+                 loss="hinge"):
+        if loss not in kernels.LOSSES:
+            raise ValueError(f"loss must be one of {kernels.LOSSES}, got {loss!r}")
+        self.loss = loss
         self.embeddings = embeddings
         self.latent_inters = latent_inters
         self.latent_varies = latent_varies
@@ -186,7 +195,9 @@ class DecagonOptimizer:
         self.predictions = Node("optimizer/predictions", fn)
 
     def _build(self):
-        self.cost = self._hinge_loss(self.outputs, self.neg_outputs)
+        # (the reference builds the hinge; its _xent_loss is the commented alternative, :111-112)
+        build = self._hinge_loss if self.loss == "hinge" else self._xent_loss
+        self.cost = build(self.outputs, self.neg_outputs)
         self.optimizer = "adam"  # tf.train.AdamOptimizer(learning_rate=FLAGS.learning_rate)
         self.opt_op = Operation("optimizer/opt_op", lambda ctx: self._train(ctx, apply=True), training=True)
         self.grads_vars = Node("optimizer/grads_vars", lambda ctx: self._train(ctx, apply=False))
@@ -248,7 +259,11 @@ class DecagonOptimizer:
         """One training step (apply) or the gradients only (compute_gradients)."""
         self._check_training(ctx)
         model = self._model()
+        if self.loss != "hinge" and getattr(ctx.session, "shard", None) is not None:
+            raise NotImplementedError(f"loss={self.loss!r} trains on one GPU (the session is sharded)")
         fwd, tp = self._train_plan(ctx, model)
+        if self.loss != "hinge" and tp.sharded:
+            raise NotImplementedError(f"loss={self.loss!r} trains on one GPU (the plan is sharded)")
         pos, neg, _, negs_dev = ctx.value(self._decode)
         e, rt, ct = self._edge(ctx)
         row_t, col_t = self._tables(ctx, rt, ct)
@@ -260,7 +275,8 @@ class DecagonOptimizer:
         dec_grads, outs = self._decoder_grads(ctx, model, e, rt, ct)
         if outs["dl"] is not None and l is None:
             raise RuntimeError("DEDICOM decoder without its diagonal")
-        op = kernels.PreparedDecoderGrad(row_t, col_t, rows, cols, negs, pos, neg, G, l, self.margin, **outs)
+        op = kernels.PreparedDecoderGrad(row_t, col_t, rows, cols, negs, pos, neg, G, l, self.margin, **outs,
+                                         loss=self.loss, neg_weight=self.neg_sample_weights)
 
         def decoder_grad(dE):
             op()
@@ -323,7 +339,7 @@ class DecagonOptimizer:
         return Node("optimizer/cost", fn)
 
     def _xent_loss(self, aff, neg_aff):
-        """optimizer.py:122-127."""
+        """optimizer.py:122-127: sum(softplus(-pos)) + neg_sample_weights * sum(softplus(neg))."""
         def fn(ctx):
             pos = runtime.as_device_f32(ctx.value(aff))
             neg = runtime.as_device_f32(ctx.value(neg_aff))

@@ -1,4 +1,5 @@
-"""One training step on a batch of EVERY relation: the summed hinge cost Σ_(i,j) Σ_k cost_ijk.
+"""One training step on a batch of EVERY relation: the summed cost Σ_(i,j) Σ_k cost_ijk (the hinge,
+or the cross-entropy of an optimizer built with loss="xent").
 
 The reference trains one (relation, batch) at a time (decagon/deep/optimizer.py:108-114 driven by
 decagon/deep/minibatch.py:278-313): every step pays the whole two-layer forward, the whole
@@ -9,10 +10,12 @@ sum of the gradients.  `train_step_all` therefore takes a batch of every relatio
 and runs one GCN backward and one Adam update: gradient accumulation over relations.
 
 Per edge type: one sampler call (dg_unigram_sample_slots, unless the negatives are fed), one
-scorer launch over the positive and negative pairs (dg_decoder_score_seg_f32), one hinge sum
-(dg_hinge_loss_ws_f32), one segmented decoder gradient (dg_decoder_grad_seg_f32) and two
-row reductions into dE (dg_segment_rows_sum_f32 over node-major occurrence lists, built by
-one stable device sort each).  The forward, the TrainPlan, the dropout masks, the embeddings
+scorer launch over the positive and negative pairs (dg_decoder_score_seg_f32), one cost sum
+(dg_hinge_loss_ws_f32 / dg_xent_loss_ws_f32), one segmented decoder gradient
+(dg_decoder_grad_seg_f32 / dg_decoder_grad_seg_xent_f32) and two row reductions into dE
+(dg_segment_rows_sum_f32 over node-major occurrence lists, built by one stable device sort
+each; the row side's weights are −1 / +1 for the hinge and the kernel's `coef` for the
+cross-entropy).  The forward, the TrainPlan, the dropout masks, the embeddings
 tables and the Adam slots are those of `opt_op`, so all-relation steps and ordinary steps mix.
 
 The batches are host dicts, packed and uploaded per step, or an epochs.DeviceBatches formed on the
@@ -185,7 +188,7 @@ def _cached_latents(ctx: RunContext, rec: dict, dec, d: int):
 
 
 def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None, apply: bool = True):
-    """One step on Σ_(i,j) Σ_k hinge cost of relation k's batch (module docstring).
+    """One step on Σ_(i,j) Σ_k cost of relation k's batch, the cost being opt.loss's (module docstring).
 
     batches: {(i, j): {k: int array [n_k, 2]}} (pack_batches' input).  neg_samples, in the same
     nesting ({(i, j): {k: int array [n_k]}}), feeds the negative rows; None draws relation k's
@@ -264,10 +267,15 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
             scores = kernels.decoder_score_seg(row_t, col_t, torch.cat([rows, negs]), torch.cat([cols, cols]), tb.seg2,
                                                G, l, seg_rel=tb.rel2)
             pos, neg = scores[:n], scores[n:]
-            costs.append(kernels.hinge_loss(pos, neg, opt.margin, workspace=kernels.hinge_workspace(dev)))
+            if opt.loss == "hinge":
+                costs.append(kernels.hinge_loss(pos, neg, opt.margin, workspace=kernels.hinge_workspace(dev)))
+            else:
+                costs.append(kernels.xent_loss(pos, neg, opt.neg_sample_weights,
+                                               workspace=kernels.hinge_workspace(dev)))
             t0 = _stage("score_hinge", t0)
             op = kernels.PreparedDecoderGradSeg(row_t, col_t, rows, cols, negs, tb.seg_ptr, tb.seg_rel, pos, neg, G, l,
-                                                opt.margin, **dec.layout.grad_outputs(dec_grads[et]))
+                                                opt.margin, **dec.layout.grad_outputs(dec_grads[et]),
+                                                loss=opt.loss, neg_weight=opt.neg_sample_weights)
             work.append((i, j, n, rows, cols, negs, op))
             t0 = _stage("gradient_setup", t0)
 
@@ -275,7 +283,10 @@ def train_step_all(sess, opt, placeholders, feed_dict, batches, neg_samples=None
             for i, j, n, rows, cols, negs, op in work:
                 op()
                 node_ptr, order = kernels.occurrence_list(torch.cat([rows, negs]), dE[i].shape[0])
-                sign = torch.where(order < n, -1.0, 1.0).to(torch.float32)
+                if opt.loss == "hinge":
+                    sign = torch.where(order < n, -1.0, 1.0).to(torch.float32)
+                else:  # (−a_p for a positive row's occurrence, +b_p for a negative row's)
+                    sign = op.coef.index_select(0, order.long())
                 kernels.segment_rows_sum(node_ptr, torch.remainder(order, n).to(torch.int32), op.mv, dE[i], sign=sign)
                 node_ptr, order = kernels.occurrence_list(cols, dE[j].shape[0])
                 kernels.segment_rows_sum(node_ptr, order, op.grad_cols, dE[j])

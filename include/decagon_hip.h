@@ -789,6 +789,17 @@ int dg_hinge_loss_ws_f32(const float* pos, const float* neg, int32_t n, float ma
 int dg_xent_loss_f32(const float* pos, const float* neg, int32_t n, float neg_weight,
                      float* loss, void* stream);
 
+/* The same cross-entropy sum over many pairs (an all-relation step: 10^6 pairs) on up to
+ * DG_HINGE_WS_BLOCKS workgroups, with dg_hinge_loss_ws_f32's workspace contract (the same
+ * DG_HINGE_WS_BYTES buffer serves both: first word zero before the first call, zero again after
+ * every call) and its order: block b sums its contiguous chunk, the partials are added in block
+ * order (deterministic for a given n).  One fp32 term per pair,
+ *     max(x,0) - x + log1p(exp(-|x|))  at x = pos[p]   plus   w * (max(y,0) + log1p(exp(-|y|)))  at y = neg[p]
+ * with log1p(e) formed in single precision as log(1 + e) plus the first-order correction for the
+ * rounding of 1 + e.  Finite for every finite score.  optimizer.py:122-127. */
+int dg_xent_loss_ws_f32(const float* pos, const float* neg, int32_t n, float neg_weight, float* loss,
+                        void* workspace, void* stream);
+
 /* --------------------------------------------------------------------------------------
  * Training step (backward of the hinge cost + TF Adam), optimizer.py:108-114.
  * -------------------------------------------------------------------------------------- */
@@ -809,6 +820,21 @@ int dg_decoder_grad_f32(const float* row_table, int64_t ld_row, const float* col
                         const float* G, const float* l, int32_t d, float margin,
                         float* grad_rows, float* grad_cols, float* dG, float* dl, float* dG_diag,
                         void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The same backward for the sigmoid cross-entropy cost (optimizer.py:122-127)
+ *     cost = Σ_p softplus(-pos[p]) + w·Σ_p softplus(neg[p]),   w = neg_weight
+ * whose gradient w.r.t. pos[p] is -a_p and w.r.t. neg[p] +b_p with a_p = σ(-pos[p]),
+ * b_p = w·σ(neg[p]) (σ(-pos) computed directly in fp32, overflow-safe: 1 - σ(pos) would cancel):
+ *     grad_rows[p] = -a_p·M·v_p,  grad_rows[n + p] = +b_p·M·v_p,  grad_cols[p] = Mᵀ·(b_p·un_p - a_p·u_p)
+ *     dM = Σ_p (b_p·un_p - a_p·u_p)·v_pᵀ;   dG, dl, dG_diag from dM as above.
+ * The hinge is the special case a_p = b_p = [neg[p] - (pos[p] - margin) > 0].  Arguments, outputs,
+ * workspace and limits are dg_decoder_grad_f32's, with neg_weight in place of margin. */
+int dg_decoder_grad_xent_f32(const float* row_table, int64_t ld_row, const float* col_table,
+                             int64_t ld_col, const int32_t* rows, const int32_t* cols,
+                             const int32_t* neg_rows, int32_t n, const float* pos, const float* neg,
+                             const float* G, const float* l, int32_t d, float neg_weight,
+                             float* grad_rows, float* grad_cols, float* dG, float* dl, float* dG_diag,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 
 /* out[idx[q]][:] += Σ_{q' : idx[q'] = idx[q]} src[q'][:]  (occurrences summed in q' order,
  * each distinct row written once).  The gradient of tf.gather (optimizer.py:66-76).
@@ -1139,6 +1165,19 @@ int dg_row_topk_excl_f32(const float* x, int64_t ld, int32_t n_rows, int32_t n_c
  * short workspace, n_pairs + 32*n_seg >= 2^31; DG_EALIGN for row_table, col_table, G, l or the
  * workspace not 16-byte aligned, or ld_row / ld_col not a multiple of 4.
  *
+ * dg_decoder_grad_seg_xent_f32: the same pass for the sigmoid cross-entropy cost (see
+ * dg_decoder_grad_xent_f32: a_p = σ(-pos[p]), b_p = neg_weight·σ(neg[p])), with neg_weight in place
+ * of margin and one more output:
+ *     coef       float [2*n_pairs]: coef[p] = -a_p, coef[n_pairs + p] = +b_p
+ *     mv[p]      = M_k·v_p, unweighted (one row per pair, as for the hinge; a zero row where both
+ *                coefficients are zero): the gradient of the
+ *                positive row is coef[p]·mv[p], of the negative row coef[n_pairs + p]·mv[p] — the
+ *                weights go through dg_segment_rows_sum_f32's `sign` array
+ *     grad_cols[p] = M_kᵀ·(b_p·un_p - a_p·u_p),   dM_s = Σ_p (b_p·un_p - a_p·u_p)·v_pᵀ
+ * and dG, dG_diag, dl from dM_s as above.  A pair with an index outside the tables, and every pair
+ * of a segment whose relation is out of range, has both coefficients 0, zero rows, and contributes
+ * nothing.  Same limits, workspace and error codes; coef NULL with n_pairs > 0 is DG_EINVAL.
+ *
  * dg_segment_rows_sum_f32: for every output row r < n_out_rows (row r at out + r*ld_out,
  * ld_out >= d, 1 <= d <= 256)
  *
@@ -1162,6 +1201,14 @@ int dg_decoder_grad_seg_f32(const float* row_table, int64_t ld_row, int32_t n_ro
                             const float* G, int64_t g_stride, const float* l, int64_t l_stride, int32_t n_rel,
                             int32_t d, float* mv, float* grad_cols, float* dG, float* dl, float* dG_diag,
                             void* workspace, int64_t workspace_bytes, void* stream);
+int dg_decoder_grad_seg_xent_f32(const float* row_table, int64_t ld_row, int32_t n_rows, const float* col_table,
+                                 int64_t ld_col, int32_t n_cols, const int32_t* rows, const int32_t* cols,
+                                 const int32_t* neg_rows, const int32_t* seg_ptr, const int32_t* seg_rel,
+                                 int32_t n_seg, int32_t n_pairs, const float* pos, const float* neg,
+                                 float neg_weight, const float* G, int64_t g_stride, const float* l,
+                                 int64_t l_stride, int32_t n_rel, int32_t d, float* mv, float* grad_cols,
+                                 float* coef, float* dG, float* dl, float* dG_diag, void* workspace,
+                                 int64_t workspace_bytes, void* stream);
 int dg_segment_rows_sum_f32(const int32_t* node_ptr, const int32_t* item, const float* sign, int32_t n_items,
                             const float* src, int32_t n_src_rows, int32_t d, float* out, int64_t ld_out,
                             int32_t n_out_rows, void* stream);
