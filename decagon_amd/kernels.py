@@ -1798,6 +1798,12 @@ def row_producer(tensor: torch.Tensor):
     return plan, node_type
 
 
+def _pack_prepared(name: str, **values) -> list:
+    """_lib.pack for a prepared call: every argument but the trailing `stream`, which each launch adds."""
+    assert _lib.arg_index(name, "stream") == len(values)
+    return _lib.pack(name, stream=None, **values)[:-1]
+
+
 class PreparedDecoderHinge:
     """dg_decoder_hinge_f32 on fixed buffers: sampled (or given) negatives, positive and
     negative scores of n pairs and the hinge loss, in one launch.
@@ -1844,12 +1850,16 @@ class PreparedDecoderHinge:
         self._ws = torch.zeros(4 + -(-n // 8), device=dev)  # ticket word + partials (either entry point)
         self._keep = (row_table, col_table, rows, cols, G, l, alias, neg_rows)
         self.seed, self.offset = seed, offset
-        self._args = [row_table.data_ptr(), row_table.shape[1], col_table.data_ptr(), col_table.shape[1],
-                      rows.data_ptr(), cols.data_ptr(), neg_rows.data_ptr() if neg_rows is not None else None,
-                      alias.data_ptr() if alias is not None else None, alias.shape[0] if alias is not None else 0,
-                      seed, offset, n, G.data_ptr(), l.data_ptr() if l is not None else None, d, float(margin),
-                      self.pos.data_ptr(), self.neg.data_ptr(), self.neg_rows.data_ptr(), self.loss.data_ptr(),
-                      self._ws.data_ptr()]
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        shared = dict(col_table=col_table.data_ptr(), ld_col=col_table.shape[1], rows=rows.data_ptr(),
+                      cols=cols.data_ptr(), neg_rows=ptr(neg_rows), alias_table=ptr(alias),
+                      range=alias.shape[0] if alias is not None else 0, seed=seed, offset=offset, n=n, d=d,
+                      margin=float(margin), pos=self.pos.data_ptr(), neg=self.neg.data_ptr(),
+                      neg_rows_out=self.neg_rows.data_ptr(), loss=self.loss.data_ptr(),
+                      workspace=self._ws.data_ptr())  # what both entry points take
+        self._args = _pack_prepared("dg_decoder_hinge_f32", row_table=row_table.data_ptr(),
+                                    ld_row=row_table.shape[1], G=G.data_ptr(), l=ptr(l), **shared)
+        self._slots = self._call_slots("dg_decoder_hinge_f32")
         self._fn = _lib.load().dg_decoder_hinge_f32
         self.entry = "dg_decoder_hinge_f32"  # the entry point of the last call
         # row operands from the plan that makes row_table
@@ -1864,8 +1874,19 @@ class PreparedDecoderHinge:
             if Q is not None:
                 self._plan, self.Q = plan, Q
                 self._rows_fn = _lib.load().dg_decoder_hinge_rows_f32
-                a = self._args
-                self._rows_args = [Q.data_ptr(), Q.shape[1]] + a[2:12] + [d] + a[15:]
+                self._rows_args = _pack_prepared("dg_decoder_hinge_rows_f32", Q=Q.data_ptr(), ld_q=Q.shape[1],
+                                                 **shared)
+                self._rows_slots = self._call_slots("dg_decoder_hinge_rows_f32")
+
+    @staticmethod
+    def _call_slots(name: str) -> Tuple[int, int]:
+        """Where the arguments hold what a call sets anew: the seed and the offset."""
+        return _lib.arg_index(name, "seed"), _lib.arg_index(name, "offset")
+
+    def _launch(self, fn, args, slots, stream) -> None:
+        a = list(args)
+        a[slots[0]], a[slots[1]] = self.seed & (2**64 - 1), self.offset & (2**64 - 1)
+        check(fn(*a, _stream_ptr(stream)), self.entry)
 
     @property
     def attached(self) -> bool:
@@ -1888,15 +1909,11 @@ class PreparedDecoderHinge:
         # Q holds the rows of the plan's last run only if it ran since the attachment (host-side
         # check; under graph capture it sees the plan.run() captured before this call)
         if self._plan is not None and self._plan.decoder_rows_valid(self.Q):
-            a = list(self._rows_args)
-            a[9], a[10] = self.seed & (2**64 - 1), self.offset & (2**64 - 1)
             self.entry = "dg_decoder_hinge_rows_f32"
-            check(self._rows_fn(*a, _stream_ptr(stream)), self.entry)
+            self._launch(self._rows_fn, self._rows_args, self._rows_slots, stream)
             return
-        a = list(self._args)
-        a[9], a[10] = self.seed & (2**64 - 1), self.offset & (2**64 - 1)
         self.entry = "dg_decoder_hinge_f32"
-        check(self._fn(*a, _stream_ptr(stream)), self.entry)
+        self._launch(self._fn, self._args, self._slots, stream)
 
 
 # --------------------------------------------------------------------------------------
@@ -1942,11 +1959,14 @@ class PreparedDecoderGrad:
         self._rows, self._negs = rows, neg_rows
         self._keep = (row_table, col_table, rows, cols, neg_rows, pos, neg, G, l, dG, dl, dG_diag)
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        self._args = [row_table.data_ptr(), row_table.shape[1], col_table.data_ptr(), col_table.shape[1],
-                      rows.data_ptr(), cols.data_ptr(), neg_rows.data_ptr(), n, pos.data_ptr(), neg.data_ptr(),
-                      G.data_ptr(), ptr(l), d, param, self.grad_rows.data_ptr(),
-                      self.grad_cols.data_ptr(), ptr(dG), ptr(dl), ptr(dG_diag), self._ws.data_ptr(), nbytes]
-        self._name = "dg_decoder_grad_f32" if loss == "hinge" else "dg_decoder_grad_xent_f32"
+        self._name, cost = (("dg_decoder_grad_f32", {"margin": param}) if loss == "hinge" else
+                            ("dg_decoder_grad_xent_f32", {"neg_weight": param}))
+        self._args = _pack_prepared(
+            self._name, row_table=row_table.data_ptr(), ld_row=row_table.shape[1], col_table=col_table.data_ptr(),
+            ld_col=col_table.shape[1], rows=rows.data_ptr(), cols=cols.data_ptr(), neg_rows=neg_rows.data_ptr(), n=n,
+            pos=pos.data_ptr(), neg=neg.data_ptr(), G=G.data_ptr(), l=ptr(l), d=d, **cost,
+            grad_rows=self.grad_rows.data_ptr(), grad_cols=self.grad_cols.data_ptr(), dG=ptr(dG), dl=ptr(dl),
+            dG_diag=ptr(dG_diag), workspace=self._ws.data_ptr(), workspace_bytes=nbytes)
         self._fn = getattr(lib, self._name)
 
     def __call__(self, stream=None) -> None:
@@ -2025,17 +2045,20 @@ class PreparedDecoderGradSeg:
         self._ws = torch.empty(max(1, nbytes // 4), device=dev) if vars_ else None
         self._keep = (row_table, col_table, rows, cols, neg_rows, seg_ptr, seg_rel, pos, neg, G, l, dG, dl, dG_diag)
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        self._name = "dg_decoder_grad_seg_f32"
-        coef = []
+        self._name, cost = "dg_decoder_grad_seg_f32", {"margin": param}
         if loss == "xent":  # (zeros: pairs outside every segment are not written, and weigh nothing)
             self.coef = torch.zeros(2 * n, device=dev)
-            self._name, coef = "dg_decoder_grad_seg_xent_f32", [ptr(self.coef) if n else None]
-        self._args = [row_table.data_ptr(), d, ops.n_rows, col_table.data_ptr(), d, ops.n_cols,
-                      ptr(rows) if n else None, ptr(cols) if n else None, ptr(neg_rows) if n else None,
-                      seg_ptr.data_ptr(), ptr(seg_rel), n_seg, n, ptr(pos) if n else None, ptr(neg) if n else None,
-                      param, *ops.c_args(), ops.n_rel(n_seg, seg_rel is not None), d,
-                      ptr(self.mv) if n else None, ptr(self.grad_cols) if n else None, *coef, ptr(dG), ptr(dl),
-                      ptr(dG_diag), ptr(self._ws), nbytes if vars_ else 0]
+            self._name = "dg_decoder_grad_seg_xent_f32"
+            cost = {"neg_weight": param, "coef": ptr(self.coef) if n else None}
+        G_, g_stride, l_, l_stride = ops.c_args()
+        self._args = _pack_prepared(
+            self._name, row_table=row_table.data_ptr(), ld_row=d, n_rows=ops.n_rows, col_table=col_table.data_ptr(),
+            ld_col=d, n_cols=ops.n_cols, rows=ptr(rows) if n else None, cols=ptr(cols) if n else None,
+            neg_rows=ptr(neg_rows) if n else None, seg_ptr=seg_ptr.data_ptr(), seg_rel=ptr(seg_rel), n_seg=n_seg,
+            n_pairs=n, pos=ptr(pos) if n else None, neg=ptr(neg) if n else None, **cost, G=G_, g_stride=g_stride,
+            l=l_, l_stride=l_stride, n_rel=ops.n_rel(n_seg, seg_rel is not None), d=d,
+            mv=ptr(self.mv) if n else None, grad_cols=ptr(self.grad_cols) if n else None, dG=ptr(dG), dl=ptr(dl),
+            dG_diag=ptr(dG_diag), workspace=ptr(self._ws), workspace_bytes=nbytes if vars_ else 0)
         self._fn = getattr(lib, self._name)
 
     def __call__(self, stream=None) -> None:

@@ -4,9 +4,9 @@ arrays and integer device addresses, so its layout can be built and checked with
 kernels.PreparedFusedTab / PreparedSegTab validate their tensors, hand them over as SegData /
 ProjData / DecData, and upload the HostTable that fused_table / seg_table return.
 
-This file holds the one Python definition of the 64-byte descriptor (DESC) and of the bit fields
-of its `role`, `wr` and `gwaves` words; the constants mirror the header's DG_TAB_* macros
-(tests/test_cpu_wavetable.py compares the two).
+This file holds the numpy form of the 64-byte descriptor (DESC; tests/test_cpu_abi.py compares it
+with the header's dg_tab_desc); the bit fields of its `role`, `wr` and `gwaves` words are the
+header's DG_TAB_* macros, read from it by abi.py.
 """
 from __future__ import annotations
 
@@ -15,6 +15,11 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
+# the bit fields of dg_tab_desc's role, wr and gwaves words (the header documents each beside its macro)
+from .abi import (DG_TAB_GWAVES_BITS, DG_TAB_MAX_ROW_SLOTS, DG_TAB_ROLE_DEC_BIT, DG_TAB_ROLE_PROJ_BIT,  # noqa: F401
+                  DG_TAB_ROLE_PROJ_SLOTS_BITS, DG_TAB_ROLE_PROJ_SLOTS_SHIFT, DG_TAB_ROLE_SEG_WAVES_BITS,
+                  DG_TAB_ROLE_SEG_WAVES_SHIFT, DG_TAB_WR_GROUPS_BITS, DG_TAB_WR_RELU_BIT, DG_TAB_WR_SLOT_SHIFT)
+
 # ---------------------------------------------------------------------------------------
 # The descriptor contract (dg_tab_desc)
 # ---------------------------------------------------------------------------------------
@@ -22,18 +27,6 @@ DESC = np.dtype([("x", "<u8"), ("w", "<u8"), ("orow", "<u8"), ("cnt", "<i4"), ("
                  ("role", "<u4"), ("wr", "<u4"), ("aux_lo", "<i4"), ("aux_hi", "<i4"), ("gwaves", "<i4"),
                  ("first_wave", "<i4"), ("reserved", "<i4")])
 assert DESC.itemsize == 64
-
-DG_TAB_ROLE_PROJ_BIT = 30          # role: the wave holds a projection job (dg_gcn_fused_tab_post_f32)
-DG_TAB_ROLE_PROJ_SLOTS_SHIFT = 24  # role: mask of the job's row slots
-DG_TAB_ROLE_PROJ_SLOTS_BITS = 4
-DG_TAB_ROLE_DEC_BIT = 29           # role: the finishing wave also stores the decoder's row operand
-DG_TAB_ROLE_SEG_WAVES_SHIFT = 8    # role: waves the first wave of a (chunk, row) sums (dg_spmm_seg_tab_f32)
-DG_TAB_ROLE_SEG_WAVES_BITS = 8
-DG_TAB_WR_GROUPS_BITS = 8          # wr bits 0-7: groups of the row
-DG_TAB_WR_RELU_BIT = 8             # wr: relu the finished row
-DG_TAB_WR_SLOT_SHIFT = 16          # wr bits 16+: the row slot
-DG_TAB_GWAVES_BITS = 4             # gwaves: (wave count - 1) of group u in bits 4u .. 4u + 3
-DG_TAB_MAX_ROW_SLOTS = 4           # rows a workgroup finishes, at most
 
 PROJ_ROW_BYTES = 32 * 4            # a P or Q row: 32 floats
 W_SLAB_BYTES = 64 * 32 * 4         # one relation's W slab

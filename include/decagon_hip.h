@@ -1042,8 +1042,8 @@ int64_t dg_rank_metrics_seg_workspace(int32_t n_pos_total, int32_t n_neg_total, 
 int dg_rank_metrics_seg_f32(const float* pos, const int32_t* pos_ptr, int32_t n_pos_total, const float* neg,
                             const int32_t* neg_ptr, int32_t n_neg_total, int32_t n_seg, int32_t k, int32_t mode,
                             double* out, void* workspace, int64_t workspace_bytes, void* stream);
-int32_t dg_seg_tile_lookup(const int32_t* seg_ptr, int32_t n_seg, int32_t tile, int32_t vt, int32_t* seg,
-                           int32_t* local);
+int32_t dg_seg_tile_lookup(const int32_t* seg_ptr, int32_t n_seg, int32_t tile, int32_t vt, int32_t* /* HOST out */ seg,
+                           int32_t* /* HOST out */ local);
 
 /* --------------------------------------------------------------------------------------
  * The profile of node pairs: every relation of one edge type scored for given pairs, and the

@@ -53,7 +53,7 @@ def test_is_identity():
 
 def _declared_symbols():
     hdr = (ROOT / "include" / "decagon_hip.h").read_text()
-    return sorted(set(re.findall(r"^\s*(?:int|int32_t|int64_t)\s+(dg_\w+)\s*\(", hdr, re.M)))
+    return sorted(set(re.findall(r"^\s*(?:int|int32_t|int64_t|uint32_t)\s+(dg_\w+)\s*\(", hdr, re.M)))
 
 
 def test_library_exports_every_declared_symbol():
