@@ -1,4 +1,4 @@
-"""ctypes binding of libdecagon_hip.so (include/decagon_hip.h).
+"""ctypes binding of libdecagon_hip.so (include/decagon_hip.h and include/decagon_hip_ext.h).
 
 This is the one place the Python layer touches native code.  There is no fallback: if the
 library is missing or fails to load, importing the compute path raises, and every op of the
@@ -11,26 +11,29 @@ import threading
 from pathlib import Path
 
 from . import _build, abi
-from .abi import SIGNATURES  # name -> (restype, argtypes), as include/decagon_hip.h declares them
+# name -> (restype, argtypes), as include/decagon_hip.h and include/decagon_hip_ext.h declare them
+SIGNATURES = {name: (p.restype, p.argtypes) for name, p in abi.ALL_PROTOTYPES.items()}
 from .tuning import knob
 
 ABI_VERSION = 39  # what this Python layer expects of dg_abi_version()
 globals().update(abi.CONSTANTS)  # every DG_* macro of the header
 globals().update(abi.STRUCTS)    # DgRelGroup, ...: the ctypes.Structure of every dg_* struct
+globals().update(abi.EXT.constants)
+globals().update({cls.__name__: cls for cls in abi.EXT.structs.values()})
 
 _ERRS = {code: name for name, code in abi.CONSTANTS.items() if name.startswith("DG_E") and code < 0}
 
 
 def arg_index(name: str, param: str) -> int:
     """The position of parameter `param` of entry point `name`."""
-    if param not in abi.PROTOTYPES[name].names:
+    if param not in abi.ALL_PROTOTYPES[name].names:
         raise TypeError(f"{name} has no parameter {param!r}")
-    return abi.PROTOTYPES[name].names.index(param)
+    return abi.ALL_PROTOTYPES[name].names.index(param)
 
 
 def pack(name: str, **values) -> list:
     """The positional argument list of entry point `name` from its arguments by parameter name."""
-    names = abi.PROTOTYPES[name].names
+    names = abi.ALL_PROTOTYPES[name].names
     missing, unknown = [p for p in names if p not in values], [v for v in values if v not in names]
     if missing or unknown:
         raise TypeError(f"{name}: missing arguments {missing}, unknown arguments {unknown}")

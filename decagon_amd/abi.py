@@ -1,6 +1,9 @@
 """The C ABI as include/decagon_hip.h declares it, parsed once at import: constants, structs and
 prototypes.  Host only and standard library only; nothing here loads the shared library.
 
+include/decagon_hip_ext.h, the entry points added after the 78 of ABI 39, is parsed by the same
+parser into a table of its own (EXT), with the first header's constants and structs in scope.
+
 The parser accepts the subset of C the header is written in and raises AbiError
 with the header line on anything else: it never guesses a type.
 """
@@ -14,6 +17,7 @@ from typing import Dict, List, NamedTuple, Optional, Tuple
 from . import _build
 
 HEADER = _build.INCLUDE / "decagon_hip.h"
+EXT_HEADER = _build.INCLUDE / "decagon_hip_ext.h"
 
 _INTS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
          "uint64_t": ctypes.c_uint64, "unsigned long long": ctypes.c_uint64, "uint16_t": ctypes.c_uint16}
@@ -24,6 +28,7 @@ _ITEM = re.compile(r'(?:(#[^\n]*)|(@HOST|\}|extern\s*"C"\s*\{)|([^;#{}]*(?:\{[^{
 _SPACE = re.compile(r"\s*")
 _DEFINE = re.compile(r"#\s*define\s+(\w+)\s*(.*)")
 _IGNORED = re.compile(r"#\s*(include|ifdef|ifndef|endif)\b")
+_GUARD = re.compile(r"DECAGON_HIP(_[A-Z0-9]+)*_H$")  # DECAGON_HIP_H, DECAGON_HIP_EXT_H
 _STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{(.*)\}\s*(\w+)\s*;$", re.S)
 _FIELD = re.compile(r"([^;]*);[ \t]*(@HOST)?")
 _PROTO = re.compile(r"([^()]*)\(([^()]*)\)\s*;$")
@@ -141,14 +146,16 @@ def _prototype(head: str, params: str, abi: Abi, where, line: int) -> None:
     abi.prototypes[name] = Prototype(restype, argtypes, tuple(names))
 
 
-def parse(text: str, name: str = HEADER.name) -> Abi:
-    """Constants, structs and prototypes of header `text`; `name` prefixes the error messages."""
+def parse(text: str, name: str = HEADER.name, base: Optional[Abi] = None) -> Abi:
+    """Constants, structs and prototypes of header `text`; `name` prefixes the error messages.
+    With `base`, the table of a header that `text` includes, that header's constants and structs
+    are in scope; the result holds only what `text` itself declares."""
     def comment(m):  # keep a HOST marker and the line count, drop the words
         return ("@HOST" if re.search(r"\bHOST\b", m.group()) else " ") + "\n" * m.group().count("\n")
 
     text = _COMMENT.sub(comment, text).rstrip()
     where = lambda line: f"{name}:{line}"  # noqa: E731
-    abi, protos, pos = Abi({}, {}, {}), [], 0
+    abi, protos, pos = Abi(dict(base.constants) if base else {}, dict(base.structs) if base else {}, {}), [], 0
     while pos < len(text):
         pos = _SPACE.match(text, pos).end()
         m, line = _ITEM.match(text, pos), text.count("\n", 0, pos) + 1
@@ -159,7 +166,7 @@ def parse(text: str, name: str = HEADER.name) -> Abi:
             d = _DEFINE.match(directive)
             if d and d.group(1).startswith("DG_"):
                 abi.constants[d.group(1)] = _evaluate(_TOKEN.findall(d.group(2)), abi.constants, where(line))
-            elif not (d and d.group(1) == "DECAGON_HIP_H") and not _IGNORED.match(directive):
+            elif not (d and _GUARD.match(d.group(1)) and not d.group(2).strip()) and not _IGNORED.match(directive):
                 raise AbiError(f"{where(line)}: unsupported directive `{directive}`")
         elif decl:
             s, p = _STRUCT.match(decl), _PROTO.match(decl)
@@ -171,6 +178,9 @@ def parse(text: str, name: str = HEADER.name) -> Abi:
                 raise AbiError(f"{where(line)}: cannot classify `{' '.join(decl.split())[:80]}`")
     for head, params, line in protos:
         _prototype(head, params, abi, where, line)
+    if base:
+        own = lambda table, seen: {k: v for k, v in table.items() if k not in seen}  # noqa: E731
+        return Abi(own(abi.constants, base.constants), own(abi.structs, base.structs), abi.prototypes)
     return abi
 
 
@@ -178,5 +188,11 @@ ABI = parse(HEADER.read_text())
 CONSTANTS, PROTOTYPES = ABI.constants, ABI.prototypes
 STRUCTS = {cls.__name__: cls for cls in ABI.structs.values()}  # by class name: DgRelGroup, ...
 SIGNATURES = {name: (p.restype, p.argtypes) for name, p in PROTOTYPES.items()}
+EXT = parse(EXT_HEADER.read_text(), EXT_HEADER.name, base=ABI)  # added after the 78 of ABI 39
+if set(EXT.prototypes) & set(PROTOTYPES):
+    raise AbiError(f"{EXT_HEADER.name} redeclares {sorted(set(EXT.prototypes) & set(PROTOTYPES))}")
+ALL_PROTOTYPES = {**PROTOTYPES, **EXT.prototypes}  # both tables: what _lib types, packs and indexes
 globals().update(CONSTANTS)
 globals().update(STRUCTS)
+globals().update(EXT.constants)
+globals().update({cls.__name__: cls for cls in EXT.structs.values()})

@@ -31,6 +31,12 @@ per relation id, main/Predictor/NpPredictor.py:293-313): one launch over pairs Ã
 (dg_decoder_score_cross_f32) and a per-pair selection on the device (dg_row_topk_f32), with
 top_relations(exclude=) outside each pair's known relations (dg_row_topk_excl_f32) â€” the reference's
 drop of the known edges on the host after _predictEdges.
+
+edge_ranks and ranking_scores_all answer "given drug u and side effect k, where does the held-out
+partner v stand among all partners u could have?" â€” the filtered rank of link prediction, and from
+it mean reciprocal rank, mean rank and Hits@h per relation (ranking_metrics).  One launch per side
+(dg_decoder_edge_rank_f32) walks every query's candidates and keeps a count; the reference's route is
+_predictEdges' whole matrix per relation, a dense mask and a count on the host.
 """
 from __future__ import annotations
 
@@ -478,3 +484,124 @@ def top_relations(sess, opt, placeholders, feed_dict, pairs, edge_type_ij, k: in
         out[valid] = _sigmoid_host(s[valid], sigmoid)
         s = out
     return s, rel, n
+
+
+RANK_SIDES = ("col", "row", "both")
+
+
+def edge_ranks(sess, opt, placeholders, feed_dict, edges, edge_type_ij, relations=None, exclude=None,
+               side: str = "col", no_self: bool = False) -> dict:
+    """The filtered rank of held-out edges of edge type (i, j) â€” "given drug u and side effect k,
+    where does the held-out partner v stand among all partners u could have?" â€” for every listed
+    relation in one launch per side (dg_decoder_edge_rank_f32).
+
+    What the reference offers is NpPredictor._predictEdges (main/Predictor/NpPredictor.py:293-313)
+    per relation id: the whole N_iÃ—N_j matrix, then a dense mask of the known edges and a count on
+    the host.  Here: one sess.run at dropout 0, one upload of the packed indices, one launch per
+    side and one copy back; no N_iÃ—N_j matrix is formed.  The decoder's variables are read in
+    place, so a fed latent matrix is refused (InvalidArgumentError), as is a sharded session.
+
+    edges: the held-out positives as accuracy_scores_all takes them, edges[(i, j)][r] = [n, 2]
+    (row node, column node); an index outside the tables raises ValueError (pack_edge_samples).
+    relations: the relations to rank, in order (default: all).  exclude: None, a
+    sparse.ExclusionCSR over all relations of the edge type, or one entry per relation as
+    sparse.exclusion_csr takes them (e.g. the adjacencies): the known partners a query does not
+    compete with â€” the query's own partner always stays a candidate.  side="col" ranks edge
+    (u, v)'s column v among the columns of row u; "row" ranks u among the rows of column v (the
+    same call with the tables swapped, G transposed per relation and the exclusion transposed;
+    ties then go to the smaller row); "both" does both.  no_self drops the candidate that is the
+    query node itself (square edge types).
+
+    Returns {"relations": int32 [n_sel], "seg_ptr": int32 [n_sel + 1], and per side ("col" / "row")
+    {"rank": int32 [n], "cand": int32 [n], "score": float32 [n]}}: query q of relation relations[s]
+    lies in [seg_ptr[s], seg_ptr[s+1]), in the order of `edges`; 1 <= rank <= cand."""
+    from .graph import InvalidArgumentError
+    from .sparse import exclusion_csr
+
+    if side not in RANK_SIDES:
+        raise ValueError(f"side must be one of {list(RANK_SIDES)}")
+    model = opt._model()
+    _edge_type_decoder(model, edge_type_ij, None)
+    if getattr(sess, "shard", None) is not None:
+        raise NotImplementedError("edge_ranks runs on one GPU (the session is sharded)")
+    et = tuple(edge_type_ij)
+    sides = ("col", "row") if side == "both" else (side,)
+    fd = dict(feed_dict)
+    fd[placeholders["dropout"]] = 0.0
+    packed = {}
+
+    def fn(ctx: RunContext):
+        if latent_fed(ctx, opt, model, et):
+            raise InvalidArgumentError("edge_ranks reads the decoder's variables; a latent matrix is fed")
+        K, row_t, col_t, G, l = _edge_type_operands("edge_ranks", ctx, opt, model, et)
+        shape = (row_t.shape[0], col_t.shape[0])
+        ri, ci, seg_ptr, _, rels = pack_edge_samples(edges, {}, et, K, shape, relations)
+        packed["relations"], packed["seg_ptr"] = rels, seg_ptr
+        ex = exclude
+        if ex is not None and not hasattr(ex, "rowptr"):
+            ex = exclusion_csr(ex, shape)
+        if ex is not None and (int(ex.n_rels), int(ex.n_rows), int(ex.n_cols)) != (K,) + shape:
+            raise ValueError(f"edge_ranks: exclusion of {ex.n_rels} relations, {ex.n_rows} Ã— {ex.n_cols}; "
+                             f"the edge type has {K}, {shape[0]} Ã— {shape[1]}")
+        n, n_seg = ri.size, rels.size
+        buf = torch.from_numpy(np.concatenate([ri, ci, seg_ptr, rels]).astype(np.int32)).to(ctx.session.device)
+        d_ri, d_ci, d_seg, d_rel = buf[:n], buf[n:2 * n], buf[2 * n:2 * n + n_seg + 1], buf[2 * n + n_seg + 1:]
+        out = []
+        for sd in sides:
+            if sd == "col":
+                res = kernels.decoder_edge_rank(row_t, col_t, d_ri, d_ci, d_seg, G, l, seg_rel=d_rel, exclude=ex,
+                                                no_self=no_self)
+            else:
+                res = kernels.decoder_edge_rank(col_t, row_t, d_ci, d_ri, d_seg, G.transpose(-1, -2).contiguous(), l,
+                                                seg_rel=d_rel, exclude=ex.transposed() if ex is not None else None,
+                                                no_self=no_self)
+            rank, score, cand = res
+            out += [rank, score.view(torch.int32), cand]
+        return torch.cat(out)  # one copy back
+
+    flat = np.asarray(sess.run(Node("evaluate/edge_ranks", fn), feed_dict=fd), np.int32)
+    n = flat.size // (3 * len(sides))
+    res = dict(packed)
+    for t, sd in enumerate(sides):
+        part = flat[3 * n * t:3 * n * (t + 1)]
+        res[sd] = {"rank": part[:n].copy(), "score": part[n:2 * n].view(np.float32).copy(), "cand": part[2 * n:].copy()}
+    return res
+
+
+def ranking_metrics(rank, seg_ptr, hits=(1, 3, 10)) -> np.ndarray:
+    """float64 [n_seg, 2 + len(hits)]: per segment s of `rank` (ranks >= 1 of queries
+    [seg_ptr[s], seg_ptr[s+1])) the row [MRR, mean rank, Hits@h for h in hits] â€” the mean of
+    1/rank, of rank and of (rank <= h).  An empty segment gives a row of NaN.  Host only."""
+    rank = np.asarray(rank, np.float64).reshape(-1)
+    ptr = np.asarray(seg_ptr, np.int64).reshape(-1)
+    hits = tuple(int(h) for h in hits)
+    if ptr.size < 1 or ptr[0] < 0 or np.any(np.diff(ptr) < 0) or ptr[-1] > rank.size:
+        raise ValueError("seg_ptr must ascend within the ranks")
+    if rank.size and rank[ptr[0]:ptr[-1]].min(initial=1.0) < 1:
+        raise ValueError("ranks start at 1")
+    out = np.full((ptr.size - 1, 2 + len(hits)), np.nan)
+    for s in range(ptr.size - 1):
+        r = rank[ptr[s]:ptr[s + 1]]
+        if r.size:
+            out[s] = [np.mean(1.0 / r), np.mean(r)] + [np.mean(r <= h) for h in hits]
+    return out
+
+
+def ranking_scores_all(sess, opt, placeholders, feed_dict, edges, edge_type_ij, relations=None, exclude=None,
+                       side: str = "col", no_self: bool = False, hits=(1, 3, 10), pooled: bool = False):
+    """Filtered MRR, mean rank and Hits@h of the held-out edges of every listed relation of edge
+    type (i, j): numpy float64 [n_sel, 2 + len(hits)], row s = ranking_metrics of relation
+    relations[s]'s ranks from edge_ranks (same arguments); with side="both" over the concatenation
+    of both sides' ranks.  A relation without edges gives a row of NaN.  pooled=True also returns
+    the same metrics over the queries of all listed relations, as a second value."""
+    res = edge_ranks(sess, opt, placeholders, feed_dict, edges, edge_type_ij, relations, exclude, side, no_self)
+    sides = ("col", "row") if side == "both" else (side,)
+    ptr = res["seg_ptr"].astype(np.int64)
+    per = [np.concatenate([res[sd]["rank"][ptr[s]:ptr[s + 1]] for sd in sides]) for s in range(ptr.size - 1)]
+    lens = np.zeros(len(per) + 1, np.int64)
+    np.cumsum([p.size for p in per], out=lens[1:])
+    ranks = np.concatenate(per) if per else np.zeros(0, np.int32)
+    rows = ranking_metrics(ranks, lens, hits)
+    if not pooled:
+        return rows
+    return rows, ranking_metrics(ranks, [0, ranks.size], hits)[0]

@@ -1247,6 +1247,38 @@ def decoder_score_seg(row_table: torch.Tensor, col_table: torch.Tensor, row_idx:
     return out
 
 
+def _stacked_exclusion(name, exclude, n_rows: int, n_cols: int, ks: set):
+    """(rowptr, col) of `exclude` — None, a sparse.ExclusionCSR (host arrays) or a (rowptr, col) pair
+    of tensors in that layout — checked against the tables on the host; its relation count joins `ks`."""
+    if exclude is None:
+        return None, None
+    if hasattr(exclude, "rowptr") and hasattr(exclude, "n_rels"):
+        if (exclude.n_rows, exclude.n_cols) != (n_rows, n_cols):
+            raise ValueError(f"{name}: exclusion shape does not match the tables")
+        ks.add(int(exclude.n_rels))
+        return exclude.rowptr, exclude.col
+    ex_rowptr, ex_col = exclude
+    if (ex_rowptr.numel() - 1) % n_rows:
+        raise ValueError(f"{name}: exclusion rowptr must have K·N_i + 1 entries")
+    ks.add((ex_rowptr.numel() - 1) // n_rows)
+    return ex_rowptr, ex_col
+
+
+def _exclusion_on_device(name, ex_rowptr, ex_col, K: int, n_rows: int, dev):
+    """_stacked_exclusion's pair as device int32 tensors of K relations (host arrays are uploaded);
+    (None, None) where nothing is excluded."""
+    if isinstance(ex_rowptr, np.ndarray):
+        ex_rowptr, ex_col = torch.from_numpy(ex_rowptr).to(dev), torch.from_numpy(ex_col).to(dev)
+    if ex_rowptr is not None:
+        _dev(ex_rowptr, torch.int32, "exclude rowptr")
+        _dev(ex_col, torch.int32, "exclude col")
+        if ex_rowptr.numel() != K * n_rows + 1:
+            raise ValueError(f"{name}: exclusion rowptr must have K·N_i + 1 entries")
+        if ex_col.numel() == 0:
+            ex_rowptr = ex_col = None  # nothing excluded
+    return ex_rowptr, ex_col
+
+
 def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor],
                  topk: int, exclude=None, upper: bool = False, no_diag: bool = False, stream=None
                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -1271,18 +1303,7 @@ def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tens
     if upper and n_rows != n_cols:
         raise ValueError("decoder_topk: upper needs square tables")
     ks = set() if ops.K is None else {ops.K}  # … and the exclusion's relation count
-    ex_rowptr = ex_col = None
-    if exclude is not None:
-        if hasattr(exclude, "rowptr") and hasattr(exclude, "n_rels"):
-            if (exclude.n_rows, exclude.n_cols) != (n_rows, n_cols):
-                raise ValueError("decoder_topk: exclusion shape does not match the tables")
-            ks.add(int(exclude.n_rels))
-            ex_rowptr, ex_col = exclude.rowptr, exclude.col
-        else:
-            ex_rowptr, ex_col = exclude
-            if (ex_rowptr.numel() - 1) % n_rows:
-                raise ValueError("decoder_topk: exclusion rowptr must have K·N_i + 1 entries")
-            ks.add((ex_rowptr.numel() - 1) // n_rows)
+    ex_rowptr, ex_col = _stacked_exclusion("decoder_topk", exclude, n_rows, n_cols, ks)
     if len(ks) > 1:
         raise ValueError(f"decoder_topk: relation counts disagree: {sorted(ks)}")
     K = ks.pop() if ks else 1
@@ -1290,15 +1311,7 @@ def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tens
         raise ValueError("decoder_topk: no relations")
     _need_device(ops.tabs)
     dev = G.device
-    if isinstance(ex_rowptr, np.ndarray):
-        ex_rowptr, ex_col = torch.from_numpy(ex_rowptr).to(dev), torch.from_numpy(ex_col).to(dev)
-    if ex_rowptr is not None:
-        _dev(ex_rowptr, torch.int32, "exclude rowptr")
-        _dev(ex_col, torch.int32, "exclude col")
-        if ex_rowptr.numel() != K * n_rows + 1:
-            raise ValueError("decoder_topk: exclusion rowptr must have K·N_i + 1 entries")
-        if ex_col.numel() == 0:
-            ex_rowptr = ex_col = None  # nothing excluded
+    ex_rowptr, ex_col = _exclusion_on_device("decoder_topk", ex_rowptr, ex_col, K, n_rows, dev)
     lib = _lib.load()
     nbytes = int(lib.dg_decoder_topk_workspace(K, n_rows, n_cols, topk))
     ws = torch.empty(-(-nbytes // 8), dtype=torch.int64, device=dev)
@@ -1314,6 +1327,73 @@ def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tens
         cols.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream_ptr(stream)),
         "dg_decoder_topk_f32")
     return scores, rows, cols, counts
+
+
+def decoder_edge_rank(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: torch.Tensor,
+                      col_idx: torch.Tensor, seg_ptr: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor],
+                      seg_rel: Optional[torch.Tensor] = None, exclude=None, no_self: bool = False, stream=None,
+                      column_split: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(rank int32, score float32, cand int32), one entry per query: the filtered rank of held-out
+    edges in one launch (dg_decoder_edge_rank_f32).  Query q = (row_idx[q], col_idx[q]) = (r, c) of
+    segment s = [seg_ptr[s], seg_ptr[s+1]) has relation k = seg_rel[s] (seg_rel None: k = s); its
+    candidates are the columns c' that relation k's exclusion row of r does not hold (and, with
+    no_self, c' != r: square tables), plus c itself.  rank[q] = 1 + the candidates c' != c before c
+    under (row_table[r] ∘ l_k)ᵀ·G_k·(l_k ∘ col_table[c']) — higher score first, ties by smaller
+    column, −0 as +0; score[q] that score of (r, c); cand[q] the number of candidates, c included.
+    No N_i×N_j matrix is formed.  A query outside the tables, or of a segment whose relation lies
+    outside [0, K), gets rank 0, cand 0 and NaN.  Asynchronous; seg_ptr (device int32 [n_seg + 1],
+    ascending from 0 to the query count) is never read on the host.
+
+    G, l, seg_rel: as decoder_score_seg (d is 32 or 64).  exclude: as decoder_topk — None, a
+    sparse.ExclusionCSR (uploaded here) or a device (rowptr, col) pair; its relation count is K too.
+    column_split=False keeps every query tile's columns in one workgroup (the measured alternative
+    of DESIGN.md §20; same results)."""
+    name = "decoder_edge_rank"
+    idx = [(row_idx, "row_idx"), (col_idx, "col_idx"), (seg_ptr, "seg_ptr"), (seg_rel, "seg_rel")]
+    ops = RelOperands.build(name, row_table, col_table, G, l, WIDTHS_MFMA, idx)
+    d, n_rows, n_cols = ops.d, ops.n_rows, ops.n_cols
+    n = row_idx.numel()
+    if col_idx.numel() != n:
+        raise ValueError(f"{name}: row_idx / col_idx length mismatch")
+    n_seg = seg_ptr.numel() - 1
+    if n_seg < 1:
+        raise ValueError(f"{name}: seg_ptr must have n_seg + 1 >= 2 entries")
+    if seg_rel is not None and seg_rel.numel() != n_seg:
+        raise ValueError(f"{name}: seg_rel must have one entry per segment")
+    if n + 32 * n_seg >= 2**31:
+        raise ValueError(f"{name}: needs queries + 32·segments < 2^31")
+    if no_self and n_rows != n_cols:
+        raise ValueError(f"{name}: no_self needs square tables")
+    ks = set() if ops.K is None else {ops.K}  # … and the exclusion's relation count
+    ex_rowptr, ex_col = _stacked_exclusion(name, exclude, n_rows, n_cols, ks)
+    if len(ks) > 1:
+        raise ValueError(f"{name}: relation counts disagree: {sorted(ks)}")
+    K = ks.pop() if ks else None
+    if K is not None and K < 1:
+        raise ValueError(f"{name}: no relations")
+    if seg_rel is None and K is not None and n_seg > K:
+        raise ValueError(f"{name}: {n_seg} segments but {K} relations (pass seg_rel)")
+    _need_device(list(ops.tabs) + idx)
+    dev = G.device
+    if ex_rowptr is not None:
+        ex_rowptr, ex_col = _exclusion_on_device(name, ex_rowptr, ex_col, K, n_rows, dev)
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    score = torch.empty(n, dtype=torch.float32, device=dev)
+    cand = torch.empty(n, dtype=torch.int32, device=dev)
+    flags = (_lib.DG_EDGE_RANK_NO_SELF if no_self else 0) | (0 if column_split else _lib.DG_EDGE_RANK_NO_SPLIT)
+    fn = _lib.load().dg_decoder_edge_rank_f32
+    check(fn(*_lib.pack(
+        "dg_decoder_edge_rank_f32", row_table=row_table.data_ptr(), ld_row=d, n_rows=n_rows,
+        col_table=col_table.data_ptr(), ld_col=d, n_cols=n_cols, row_idx=row_idx.data_ptr() if n else None,
+        col_idx=col_idx.data_ptr() if n else None, seg_ptr=seg_ptr.data_ptr(),
+        seg_rel=seg_rel.data_ptr() if seg_rel is not None else None, n_seg=n_seg, n_queries=n,
+        **dict(zip(("G", "g_stride", "l", "l_stride"), ops.c_args())),
+        n_rel=K if K is not None else ops.n_rel(n_seg, seg_rel is not None), d=d,
+        excl_rowptr=ex_rowptr.data_ptr() if ex_rowptr is not None else None,
+        excl_col=ex_col.data_ptr() if ex_col is not None else None, flags=flags,
+        out_rank=rank.data_ptr() if n else None, out_score=score.data_ptr() if n else None,
+        out_cand=cand.data_ptr() if n else None, stream=_stream_ptr(stream))), "dg_decoder_edge_rank_f32")
+    return rank, score, cand
 
 
 def cross_slot_chunk(n_pairs: int, n_sel: int) -> int:

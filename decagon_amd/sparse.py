@@ -184,6 +184,19 @@ class ExclusionCSR:
     def nnz(self) -> int:
         return int(self.col.shape[0])
 
+    def transposed(self) -> "ExclusionCSR":
+        """The same sets with rows and columns swapped (host only): relation k's row c of the
+        result holds the rows r whose set held c, ascending and unique — the exclusion of a query
+        that ranks rows among rows (evaluate.edge_ranks, side="row")."""
+        n_r, n_c, K = int(self.n_rows), int(self.n_cols), int(self.n_rels)
+        counts = np.diff(self.rowptr.astype(np.int64))
+        stacked_row = np.repeat(np.arange(K * n_r, dtype=np.int64), counts)  # k·n_rows + r of every entry
+        key = (stacked_row // n_r * n_c + self.col.astype(np.int64)) * n_r + stacked_row % n_r
+        key = np.unique(key)  # by (relation, column, row); a repeated entry of a malformed input is dropped
+        rowptr = np.zeros(K * n_c + 1, np.int64)
+        np.cumsum(np.bincount(key // n_r, minlength=K * n_c), out=rowptr[1:])
+        return ExclusionCSR(rowptr.astype(np.int32), (key % n_r).astype(np.int32), n_c, n_r, K)
+
 
 def exclusion_csr(mats_or_coo_list, shape) -> ExclusionCSR:
     """Stack one exclusion set per relation for kernels.decoder_topk.  Each entry is a scipy
