@@ -18,6 +18,15 @@ INCLUDE = ROOT / "include"
 LIBDIR = PKG / "lib"
 LIBNAME = "libdecagon_hip.so"
 ARCH = knob("DG_OFFLOAD_ARCH", "gfx950")
+# Kernel-argument preload: how many leading argument dwords of each kernel the device compile asks
+# to have placed in user SGPRs when a wave is launched, so a kernel's first loads do not wait for a
+# read of its argument segment.  The limit is 16 user SGPRs minus the 2 of the argument pointer, so
+# at most 14 dwords are granted; the preload stops in front of the first by-value struct parameter
+# (a kernel that opens with one gets none), and each kernel keeps a prologue that loads the same
+# dwords for firmware that does not preload.  A variant build may give its own count as a raw flag
+# (`-mllvm -amdgpu-kernarg-preload-count=0`: the same tree without the preload).
+KERNARG_PRELOAD_COUNT = 16
+_PRELOAD_OPT = "-amdgpu-kernarg-preload-count="
 
 
 def lib_path() -> Path:
@@ -56,6 +65,10 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: Path = No
         return out
     LIBDIR.mkdir(parents=True, exist_ok=True)
     tmp = out.with_suffix(".so.tmp")
+    preload = []  # (the option may be given once: a variant's own count replaces the default)
+    if not any(_PRELOAD_OPT in d for d in defines):
+        # (-mllvm reaches the host pass too, where the AMDGPU option is known and has no effect)
+        preload = ["-mllvm", f"{_PRELOAD_OPT}{KERNARG_PRELOAD_COUNT}"]
     cmd = [
         hipcc(),
         "-O3",
@@ -67,6 +80,7 @@ def build(force: bool = False, verbose: bool = False, defines=(), out: Path = No
         "-Wno-pass-failed",
         f"-I{INCLUDE}",
         f"-I{CSRC}",
+        *preload,
         *[d if d.startswith("-") else f"-D{d}" for d in defines],  # (variants: raw flags too)
         "-o",
         str(tmp),

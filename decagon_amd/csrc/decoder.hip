@@ -79,12 +79,13 @@ extern "C" int64_t dg_dec_prof_copy(unsigned long long* host) {
 }
 #endif
 
-struct HingeArgs {
+// The fused decoders take what a wave's first memory trip needs (the index arrays, the sampler's
+// table, the pair count and the draw counters: 14 dwords) as leading plain parameters, which the
+// build's kernel-argument preload (_build.py) places in user SGPRs at wave launch; the index loads
+// and the draws go out without a read of the argument segment in front of them.  The rest, needed
+// only from the second trip on, follows as one struct and is loaded behind them.
+struct HingeRest {
     DecTab t;
-    const int32_t* rows;
-    const int32_t* cols;
-    const int32_t* neg_given;
-    const uint2* alias;
     float* pos;
     float* neg;
     int32_t* neg_rows_out;
@@ -92,15 +93,14 @@ struct HingeArgs {
     float* partial;     // [gridDim.x]
     uint32_t* ticket;   // zero before the first launch; the last block resets it
     unsigned long long* word;  // PACKED: count | out-of-range count | fixed-point sum (zero between launches)
-    uint64_t seed;
-    uint64_t offset;
-    int32_t range;
-    int32_t n;
     float margin;
 };
 
 template <bool PACKED>
-__global__ __launch_bounds__(128) void decoder_hinge_kernel(const HingeArgs a) {
+__global__ __launch_bounds__(128) void decoder_hinge_kernel(const int32_t* rows, const int32_t* cols,
+                                                            const int32_t* neg_given, const uint2* alias,
+                                                            const int32_t n, const int32_t range, const uint64_t seed,
+                                                            const uint64_t offset, const HingeRest a) {
     __shared__ float sc[2][32];
     __shared__ float red[128];
     __shared__ int last;
@@ -111,17 +111,17 @@ __global__ __launch_bounds__(128) void decoder_hinge_kernel(const HingeArgs a) {
     const int h = lane >> 5;
     const int b0 = blockIdx.x * 32;
     const int b = b0 + i;
-    const bool valid = b < a.n;
+    const bool valid = b < n;
     DG_DEC_STAMP(0);  // (profiling build: wave start)
     int ridx = 0, cidx = 0;
     if (valid) {
-        cidx = a.cols[b];
+        cidx = cols[b];
         if (side == 0)
-            ridx = a.rows[b];
-        else if (a.neg_given)
-            ridx = a.neg_given[b];
+            ridx = rows[b];
+        else if (neg_given)
+            ridx = neg_given[b];
         else
-            ridx = unigram_draw(a.alias, a.range, a.seed, a.offset + (uint64_t)b);
+            ridx = unigram_draw(alias, range, seed, offset + (uint64_t)b);
         if (side == 1 && a.neg_rows_out && h == 0) a.neg_rows_out[b] = ridx;
     }
     DG_DEC_STAMP(1);  // indices (and the negatives' draws) landed
@@ -130,14 +130,14 @@ __global__ __launch_bounds__(128) void decoder_hinge_kernel(const HingeArgs a) {
     if ((i & 1) == 0) {  // lane 2r holds score r of its half
         const int r = i >> 1;
         const int q = dg::acc_row(r, h);
-        const float v = (b0 + q < a.n) ? part[0] : 0.f;
+        const float v = (b0 + q < n) ? part[0] : 0.f;
         sc[side][q] = v;
-        if (b0 + q < a.n) (side == 0 ? a.pos : a.neg)[b0 + q] = v;
+        if (b0 + q < n) (side == 0 ? a.pos : a.neg)[b0 + q] = v;
     }
     __syncthreads();
     if (threadIdx.x < 64) {
         float term = 0.f;
-        if (lane < 32 && b0 + lane < a.n) term = fmaxf(sc[1][lane] - (sc[0][lane] - a.margin), 0.f);
+        if (lane < 32 && b0 + lane < n) term = fmaxf(sc[1][lane] - (sc[0][lane] - a.margin), 0.f);
         term = dg::xor_add<1>(dg::xor_add<2>(dg::xor_add<4>(dg::xor_add<8>(dg::xor_add<16>(dg::xor_add<32>(term))))));
         if (lane == 0 && PACKED) {
             unsigned long long add = 1ull << 56;
@@ -209,15 +209,11 @@ __global__ __launch_bounds__(128) void decoder_hinge_kernel(const HingeArgs a) {
 // flight together), a workgroup NW waves.  Draws, outputs and the hand-off are
 // decoder_hinge_kernel's: the same counters, PACKED's one returning atomic per workgroup, or
 // the sc1 partial + ticket above 255 workgroups.
-struct RowsHingeArgs {
+struct RowsHingeRest {
     const float* Q;
     const float* col_table;
     int64_t ld_q;
     int64_t ld_col;
-    const int32_t* rows;
-    const int32_t* cols;
-    const int32_t* neg_given;
-    const uint2* alias;
     float* pos;
     float* neg;
     int32_t* neg_rows_out;
@@ -225,10 +221,6 @@ struct RowsHingeArgs {
     float* partial;
     uint32_t* ticket;
     unsigned long long* word;
-    uint64_t seed;
-    uint64_t offset;
-    int32_t range;
-    int32_t n;
     float margin;
 };
 
@@ -237,7 +229,11 @@ __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
 }
 
 template <bool PACKED, int NW, int PPG>
-__global__ __launch_bounds__(64 * NW) void decoder_rows_hinge_kernel(const RowsHingeArgs a) {
+__global__ __launch_bounds__(64 * NW) void decoder_rows_hinge_kernel(const int32_t* rows, const int32_t* cols,
+                                                                   const int32_t* neg_given, const uint2* alias,
+                                                                   const int32_t n, const int32_t range,
+                                                                   const uint64_t seed, const uint64_t offset,
+                                                                   const RowsHingeRest a) {
     __shared__ float wsum[NW];
     __shared__ int last;
     __shared__ unsigned long long total;
@@ -250,10 +246,10 @@ __global__ __launch_bounds__(64 * NW) void decoder_rows_hinge_kernel(const RowsH
     for (int u = 0; u < PPG; ++u) {
         const int b = b0 + 8 * u;
         ridx[u] = nidx[u] = cidx[u] = 0;
-        if (b < a.n) {
-            cidx[u] = a.cols[b];
-            ridx[u] = a.rows[b];
-            nidx[u] = a.neg_given ? a.neg_given[b] : unigram_draw(a.alias, a.range, a.seed, a.offset + (uint64_t)b);
+        if (b < n) {
+            cidx[u] = cols[b];
+            ridx[u] = rows[b];
+            nidx[u] = neg_given ? neg_given[b] : unigram_draw(alias, range, seed, offset + (uint64_t)b);
         }
     }
     float4 ev[PPG], qp[PPG], qn[PPG];
@@ -270,7 +266,7 @@ __global__ __launch_bounds__(64 * NW) void decoder_rows_hinge_kernel(const RowsH
         float sp = dot4(qp[u], ev[u]), sn = dot4(qn[u], ev[u]);
         sp = dg::xor_add<1>(dg::xor_add<2>(dg::xor_add<4>(sp)));
         sn = dg::xor_add<1>(dg::xor_add<2>(dg::xor_add<4>(sn)));
-        if (b < a.n) {
+        if (b < n) {
             if (q == 0) {
                 a.pos[b] = sp;
                 a.neg[b] = sn;
@@ -564,13 +560,9 @@ extern "C" int dg_decoder_hinge_f32(const float* row_table, int64_t ld_row, cons
     if (ld_row < d || ld_col < d) return DG_EINVAL;
     if (!dg::aligned16(workspace)) return DG_EALIGN;
     const int blocks = dg::ceil_div(n, 32);
-    HingeArgs a{};
+    HingeRest a{};
     a.t = DecTab{row_table, col_table, G, l, ld_row, ld_col, d,
                  dg::aligned16(row_table) && (ld_row & 3) == 0 && (!l || dg::aligned16(l))};
-    a.rows = rows;
-    a.cols = cols;
-    a.neg_given = neg_rows;
-    a.alias = reinterpret_cast<const uint2*>(alias_table);
     a.pos = pos;
     a.neg = neg;
     a.neg_rows_out = neg_rows_out;
@@ -578,18 +570,17 @@ extern "C" int dg_decoder_hinge_f32(const float* row_table, int64_t ld_row, cons
     a.ticket = reinterpret_cast<uint32_t*>(workspace);
     a.word = reinterpret_cast<unsigned long long*>(workspace) + 1;
     a.partial = reinterpret_cast<float*>(workspace) + 4;
-    a.seed = seed;
-    a.offset = offset;
-    a.range = range;
-    a.n = n;
+    const uint2* alias = reinterpret_cast<const uint2*>(alias_table);
     a.margin = margin;
     // ≤ 255 workgroups: one returning 64-bit atomic per block (PACKED); more: the sc1 ticket
     if (blocks <= 255)
         hipLaunchKernelGGL(decoder_hinge_kernel<true>, dim3(blocks), dim3(128), 0,
-                           reinterpret_cast<hipStream_t>(stream), a);
+                           reinterpret_cast<hipStream_t>(stream), rows, cols, neg_rows, alias, n, range, seed, offset,
+                           a);
     else
         hipLaunchKernelGGL(decoder_hinge_kernel<false>, dim3(blocks), dim3(128), 0,
-                           reinterpret_cast<hipStream_t>(stream), a);
+                           reinterpret_cast<hipStream_t>(stream), rows, cols, neg_rows, alias, n, range, seed, offset,
+                           a);
     return dg::launch_status();
 }
 
@@ -616,15 +607,11 @@ extern "C" int dg_decoder_hinge_rows_f32(const float* Q, int64_t ld_q, const flo
     if (!dg::aligned16(workspace) || !dg::aligned16(Q) || !dg::aligned16(col_table) || (ld_q & 3) || (ld_col & 3))
         return DG_EALIGN;
     const int blocks = dg::ceil_div(n, DG_DEC_ROWS_PAIRS);
-    RowsHingeArgs a{};
+    RowsHingeRest a{};
     a.Q = Q;
     a.col_table = col_table;
     a.ld_q = ld_q;
     a.ld_col = ld_col;
-    a.rows = rows;
-    a.cols = cols;
-    a.neg_given = neg_rows;
-    a.alias = reinterpret_cast<const uint2*>(alias_table);
     a.pos = pos;
     a.neg = neg;
     a.neg_rows_out = neg_rows_out;
@@ -632,18 +619,15 @@ extern "C" int dg_decoder_hinge_rows_f32(const float* Q, int64_t ld_q, const flo
     a.ticket = reinterpret_cast<uint32_t*>(workspace);
     a.word = reinterpret_cast<unsigned long long*>(workspace) + 1;
     a.partial = reinterpret_cast<float*>(workspace) + 4;
-    a.seed = seed;
-    a.offset = offset;
-    a.range = range;
-    a.n = n;
+    const uint2* alias = reinterpret_cast<const uint2*>(alias_table);
     a.margin = margin;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // ≤ 255 workgroups: one returning 64-bit atomic per block (PACKED); more: the sc1 ticket
     if (blocks <= 255)
         hipLaunchKernelGGL((decoder_rows_hinge_kernel<true, DG_DEC_ROWS_NW, DG_DEC_ROWS_PPG>), dim3(blocks),
-                           dim3(64 * DG_DEC_ROWS_NW), 0, st, a);
+                           dim3(64 * DG_DEC_ROWS_NW), 0, st, rows, cols, neg_rows, alias, n, range, seed, offset, a);
     else
         hipLaunchKernelGGL((decoder_rows_hinge_kernel<false, DG_DEC_ROWS_NW, DG_DEC_ROWS_PPG>), dim3(blocks),
-                           dim3(64 * DG_DEC_ROWS_NW), 0, st, a);
+                           dim3(64 * DG_DEC_ROWS_NW), 0, st, rows, cols, neg_rows, alias, n, range, seed, offset, a);
     return dg::launch_status();
 }
