@@ -1,4 +1,5 @@
-"""ctypes binding of libdecagon_hip.so (include/decagon_hip.h and include/decagon_hip_ext.h).
+"""ctypes binding of libdecagon_hip.so (include/decagon_hip.h and its extension headers,
+include/decagon_hip_ext.h and include/decagon_hip_ext2.h).
 
 This is the one place the Python layer touches native code.  There is no fallback: if the
 library is missing or fails to load, importing the compute path raises, and every op of the
@@ -11,15 +12,16 @@ import threading
 from pathlib import Path
 
 from . import _build, abi
-# name -> (restype, argtypes), as include/decagon_hip.h and include/decagon_hip_ext.h declare them
+# name -> (restype, argtypes), as include/decagon_hip.h and the extension headers declare them
 SIGNATURES = {name: (p.restype, p.argtypes) for name, p in abi.ALL_PROTOTYPES.items()}
 from .tuning import knob
 
 ABI_VERSION = 39  # what this Python layer expects of dg_abi_version()
 globals().update(abi.CONSTANTS)  # every DG_* macro of the header
 globals().update(abi.STRUCTS)    # DgRelGroup, ...: the ctypes.Structure of every dg_* struct
-globals().update(abi.EXT.constants)
-globals().update({cls.__name__: cls for cls in abi.EXT.structs.values()})
+for _ext in abi.EXTENSIONS:  # decagon_hip_ext.h, decagon_hip_ext2.h
+    globals().update(_ext.constants)
+    globals().update({cls.__name__: cls for cls in _ext.structs.values()})
 
 _ERRS = {code: name for name, code in abi.CONSTANTS.items() if name.startswith("DG_E") and code < 0}
 

@@ -2,7 +2,9 @@
 prototypes.  Host only and standard library only; nothing here loads the shared library.
 
 include/decagon_hip_ext.h, the entry points added after the 78 of ABI 39, is parsed by the same
-parser into a table of its own (EXT), with the first header's constants and structs in scope.
+parser into a table of its own (EXT), with the first header's constants and structs in scope; each
+later extension header (EXT_HEADERS, in order: decagon_hip_ext2.h is EXT2) likewise, with every
+earlier table in scope.
 
 The parser accepts the subset of C the header is written in and raises AbiError
 with the header line on anything else: it never guesses a type.
@@ -18,6 +20,7 @@ from . import _build
 
 HEADER = _build.INCLUDE / "decagon_hip.h"
 EXT_HEADER = _build.INCLUDE / "decagon_hip_ext.h"
+EXT_HEADERS = (EXT_HEADER, _build.INCLUDE / "decagon_hip_ext2.h")  # in the order they include one another
 
 _INTS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
          "uint64_t": ctypes.c_uint64, "unsigned long long": ctypes.c_uint64, "uint16_t": ctypes.c_uint16}
@@ -188,11 +191,29 @@ ABI = parse(HEADER.read_text())
 CONSTANTS, PROTOTYPES = ABI.constants, ABI.prototypes
 STRUCTS = {cls.__name__: cls for cls in ABI.structs.values()}  # by class name: DgRelGroup, ...
 SIGNATURES = {name: (p.restype, p.argtypes) for name, p in PROTOTYPES.items()}
-EXT = parse(EXT_HEADER.read_text(), EXT_HEADER.name, base=ABI)  # added after the 78 of ABI 39
-if set(EXT.prototypes) & set(PROTOTYPES):
-    raise AbiError(f"{EXT_HEADER.name} redeclares {sorted(set(EXT.prototypes) & set(PROTOTYPES))}")
-ALL_PROTOTYPES = {**PROTOTYPES, **EXT.prototypes}  # both tables: what _lib types, packs and indexes
+
+
+def _parse_extensions(headers) -> List[Abi]:
+    """One table per extension header, in order; each is parsed with every earlier table in scope
+    and may redeclare none of their prototypes."""
+    scope, tables = ABI, []
+    for path in headers:
+        ext = parse(path.read_text(), path.name, base=scope)
+        again = set(ext.prototypes) & set(scope.prototypes)
+        if again:
+            raise AbiError(f"{path.name} redeclares {sorted(again)}")
+        tables.append(ext)
+        scope = Abi({**scope.constants, **ext.constants}, {**scope.structs, **ext.structs},
+                    {**scope.prototypes, **ext.prototypes})
+    return tables
+
+
+EXTENSIONS = _parse_extensions(EXT_HEADERS)
+EXT, EXT2 = EXTENSIONS  # added after the 78 of ABI 39: the filtered edge rank; a node's best partners
+ALL_PROTOTYPES = {**PROTOTYPES}  # every table: what _lib types, packs and indexes
 globals().update(CONSTANTS)
 globals().update(STRUCTS)
-globals().update(EXT.constants)
-globals().update({cls.__name__: cls for cls in EXT.structs.values()})
+for _ext in EXTENSIONS:
+    ALL_PROTOTYPES.update(_ext.prototypes)
+    globals().update(_ext.constants)
+    globals().update({cls.__name__: cls for cls in _ext.structs.values()})

@@ -37,6 +37,11 @@ partner v stand among all partners u could have?" — the filtered rank of link 
 it mean reciprocal rank, mean rank and Hits@h per relation (ranking_metrics).  One launch per side
 (dg_decoder_edge_rank_f32) walks every query's candidates and keeps a count; the reference's route is
 _predictEdges' whole matrix per relation, a dense mask and a count on the host.
+
+top_partners answers the question asked first — "given drug u and side effect k, which drugs are u's
+likeliest partners outside the known ones?": the same walk with one running top-k list per query row in
+place of the count (dg_decoder_node_topk_f32, one launch pair per side; pack_node_queries packs the
+query nodes by relation on the host).
 """
 from __future__ import annotations
 
@@ -311,6 +316,49 @@ def pack_edge_samples(edges_pos, edges_neg, edge_type_ij, num_relations: int, sh
         raise ValueError("edge sample outside the embedding tables")
     return (np.ascontiguousarray(allp[:, 0], np.int32), np.ascontiguousarray(allp[:, 1], np.int32),
             ptrs[0].astype(np.int32), ptrs[1].astype(np.int32), rels.astype(np.int32))
+
+
+def pack_node_queries(nodes, num_relations: int, n_nodes: int, relations=None):
+    """The query nodes of the relations of an edge type, packed for one fused top_partners call
+    (host only): (node_idx, seg_ptr, relations), all numpy int32.
+
+    node_idx holds the nodes of every listed relation, relation by relation in the order of
+    `relations` (default: 0 .. num_relations − 1); relation relations[s]'s are
+    node_idx[seg_ptr[s]:seg_ptr[s+1]], in the order given.  `nodes` is a 1-D integer array (the same
+    nodes for every listed relation) or a mapping {relation: array}; there a relation that is
+    missing, None or empty gives an empty segment.  A node outside [0, n_nodes), a relation (listed,
+    or a key of the mapping) outside [0, num_relations), a key of the mapping that is not among
+    the listed relations and an array that is not 1-D raise ValueError."""
+    rels = np.arange(num_relations, dtype=np.int64) if relations is None else np.asarray(relations, np.int64).reshape(-1)
+    if rels.size < 1:
+        raise ValueError("no relations to query")
+    if rels.min() < 0 or rels.max() >= num_relations:
+        raise ValueError(f"relation outside [0, {num_relations})")
+
+    def one(a):
+        a = np.zeros(0, np.int64) if a is None else np.asarray(a)
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError("nodes must be 1-D integer arrays")
+        return a.astype(np.int64)
+
+    if hasattr(nodes, "keys"):
+        if any(not 0 <= int(r) < num_relations for r in nodes.keys()):
+            raise ValueError(f"relation outside [0, {num_relations})")
+        unlisted = sorted({int(r) for r in nodes.keys()} - set(rels.tolist()))
+        if unlisted:
+            raise ValueError(f"nodes given for relations {unlisted}, which are not among those listed")
+        per = {int(r): one(a) for r, a in nodes.items()}
+        chunks = [per.get(int(r), np.zeros(0, np.int64)) for r in rels]
+    else:
+        chunks = [one(nodes)] * rels.size
+    ptr = np.zeros(rels.size + 1, np.int64)
+    np.cumsum([c.size for c in chunks], out=ptr[1:])
+    idx = np.concatenate(chunks)
+    if idx.size + 32 * rels.size >= 2**31:
+        raise ValueError("too many queries for 32-bit offsets")
+    if idx.size and (idx.min() < 0 or idx.max() >= n_nodes):
+        raise ValueError("query node outside the embedding table")
+    return idx.astype(np.int32), ptr.astype(np.int32), rels.astype(np.int32)
 
 
 def accuracy_scores_all(sess, opt, placeholders, feed_dict, edges_pos, edges_neg, edge_type_ij, relations=None,
@@ -605,3 +653,97 @@ def ranking_scores_all(sess, opt, placeholders, feed_dict, edges, edge_type_ij, 
     if not pooled:
         return rows
     return rows, ranking_metrics(ranks, [0, ranks.size], hits)[0]
+
+
+def top_partners(sess, opt, placeholders, feed_dict, nodes, edge_type_ij, k: int, relations=None, exclude=None,
+                 side: str = "col", no_self: bool = False, sigmoid: Optional[str] = None) -> dict:
+    """For given nodes and every listed relation of edge type (i, j), each node's k best permitted
+    partners — "given drug u and side effect k, which drugs are u's likeliest partners outside the
+    known ones?" — in one launch pair per side (dg_decoder_node_topk_f32).
+
+    What the reference offers is NpPredictor._predictEdges (main/Predictor/NpPredictor.py:293-313)
+    per relation id: the whole N_i×N_j matrix, a dense mask of the known edges and a sort of each
+    wanted row on the host.  Here: one sess.run at dropout 0, one upload of the packed indices
+    (pack_node_queries), one launch pair per side and one copy back; no N_i×N_j matrix is formed.
+    The decoder's variables are read in place, so a fed latent matrix is refused
+    (InvalidArgumentError), as is a sharded session.
+
+    nodes: a 1-D integer array (the same nodes for every listed relation) or {relation: array}; a
+    node outside the table raises ValueError.  relations: the relations to query, in order
+    (default: all).  exclude: as edge_ranks takes it — None, a sparse.ExclusionCSR over all
+    relations of the edge type, or one entry per relation as sparse.exclusion_csr takes them (e.g.
+    the adjacencies): the known partners, which are not listed.  side="col" lists the best column
+    nodes of a row node; "row" the best row nodes of a column node (the same call with the tables
+    swapped, G transposed per relation and the exclusion transposed; ties then go to the smaller
+    row); "both" does both, and then a node must lie in both tables.  no_self drops the query node
+    itself (square edge types).  k in [1, DG_NODE_TOPK_MAX_K].
+
+    The ranking is by LOGIT (ties by the smaller partner); `sigmoid` (a key of SIGMOID_MODES) only
+    transforms the returned scores, as in top_candidates.
+
+    Returns {"relations": int32 [n_sel], "seg_ptr": int32 [n_sel + 1], "nodes": int32 [n], and per
+    side ("col" / "row") {"partner": int32 [n, k], "score": [n, k], "count": int32 [n]}}: query q
+    of relation relations[s] lies in [seg_ptr[s], seg_ptr[s+1]), in the order of `nodes`;
+    count = min(k, permitted partners), slots past it hold −1 / −inf."""
+    from .graph import InvalidArgumentError
+    from .sparse import exclusion_csr
+
+    if side not in RANK_SIDES:
+        raise ValueError(f"side must be one of {list(RANK_SIDES)}")
+    model = opt._model()
+    _edge_type_decoder(model, edge_type_ij, sigmoid)
+    k = int(k)
+    if not 1 <= k <= _lib.DG_NODE_TOPK_MAX_K:
+        raise ValueError(f"top_partners: k must be in [1, {_lib.DG_NODE_TOPK_MAX_K}]")
+    if getattr(sess, "shard", None) is not None:
+        raise NotImplementedError("top_partners runs on one GPU (the session is sharded)")
+    et = tuple(edge_type_ij)
+    sides = ("col", "row") if side == "both" else (side,)
+    fd = dict(feed_dict)
+    fd[placeholders["dropout"]] = 0.0
+    packed = {}
+
+    def fn(ctx: RunContext):
+        if latent_fed(ctx, opt, model, et):
+            raise InvalidArgumentError("top_partners reads the decoder's variables; a latent matrix is fed")
+        K, row_t, col_t, G, l = _edge_type_operands("top_partners", ctx, opt, model, et)
+        shape = (row_t.shape[0], col_t.shape[0])
+        n_nodes = min(shape) if side == "both" else shape[0] if side == "col" else shape[1]
+        idx, seg_ptr, rels = pack_node_queries(nodes, K, n_nodes, relations)
+        packed["relations"], packed["seg_ptr"], packed["nodes"] = rels, seg_ptr, idx
+        ex = exclude
+        if ex is not None and not hasattr(ex, "rowptr"):
+            ex = exclusion_csr(ex, shape)
+        if ex is not None and (int(ex.n_rels), int(ex.n_rows), int(ex.n_cols)) != (K,) + shape:
+            raise ValueError(f"top_partners: exclusion of {ex.n_rels} relations, {ex.n_rows} × {ex.n_cols}; "
+                             f"the edge type has {K}, {shape[0]} × {shape[1]}")
+        n, n_seg = idx.size, rels.size
+        buf = torch.from_numpy(np.concatenate([idx, seg_ptr, rels]).astype(np.int32)).to(ctx.session.device)
+        d_idx, d_seg, d_rel = buf[:n], buf[n:n + n_seg + 1], buf[n + n_seg + 1:]
+        out = []
+        for sd in sides:
+            if sd == "col":
+                res = kernels.decoder_node_topk(row_t, col_t, d_idx, d_seg, G, l, k, seg_rel=d_rel, exclude=ex,
+                                                no_self=no_self)
+            else:
+                res = kernels.decoder_node_topk(col_t, row_t, d_idx, d_seg, G.transpose(-1, -2).contiguous(), l, k,
+                                                seg_rel=d_rel, exclude=ex.transposed() if ex is not None else None,
+                                                no_self=no_self)
+            score, col, count = res
+            out += [score.view(torch.int32).reshape(-1), col.reshape(-1), count]
+        return torch.cat(out)  # one copy back
+
+    flat = np.asarray(sess.run(Node("evaluate/top_partners", fn), feed_dict=fd), np.int32)
+    n = flat.size // ((2 * k + 1) * len(sides))
+    res = dict(packed)
+    for t, sd in enumerate(sides):
+        part = flat[(2 * k + 1) * n * t:(2 * k + 1) * n * (t + 1)]
+        s = part[:n * k].view(np.float32).reshape(n, k).copy()
+        count = part[2 * n * k:].copy()
+        if sigmoid is not None:
+            valid = np.arange(k)[None, :] < count[:, None]
+            out = np.full(s.shape, -np.inf, np.float64 if sigmoid == "main" else np.float32)
+            out[valid] = _sigmoid_host(s[valid], sigmoid)
+            s = out
+        res[sd] = {"partner": part[n * k:2 * n * k].reshape(n, k).copy(), "score": s, "count": count}
+    return res

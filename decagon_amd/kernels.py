@@ -1396,6 +1396,76 @@ def decoder_edge_rank(row_table: torch.Tensor, col_table: torch.Tensor, row_idx:
     return rank, score, cand
 
 
+def decoder_node_topk(row_table: torch.Tensor, col_table: torch.Tensor, row_idx: torch.Tensor,
+                      seg_ptr: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor], topk: int,
+                      seg_rel: Optional[torch.Tensor] = None, exclude=None, no_self: bool = False,
+                      column_split: bool = True, stream=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(scores float32 [n, topk], cols int32 [n, topk], counts int32 [n]): every query node's topk
+    best permitted partners in one fused launch pair (dg_decoder_node_topk_f32).  Query q =
+    row_idx[q] = r of segment s = [seg_ptr[s], seg_ptr[s+1]) has relation k = seg_rel[s] (seg_rel
+    None: k = s); its permitted columns are those relation k's exclusion row of r does not hold
+    (and, with no_self, c' != r: square tables).  They are ranked under
+    (row_table[r] ∘ l_k)ᵀ·G_k·(l_k ∘ col_table[c']) — higher score first, ties by smaller column,
+    −0 as +0; counts[q] = min(topk, permitted columns), and slots past it hold −inf / −1.  No
+    N_i×N_j matrix is formed.  A query outside the table, or of a segment whose relation lies
+    outside [0, K), gets count 0.  Asynchronous; seg_ptr (device int32 [n_seg + 1], ascending from
+    0 to the query count) is never read on the host.
+
+    G, l, seg_rel, exclude: as decoder_edge_rank (d is 32 or 64).  column_split=False keeps every
+    query tile's columns in one workgroup (the measured alternative of DESIGN.md §21; same
+    results)."""
+    name = "decoder_node_topk"
+    idx = [(row_idx, "row_idx"), (seg_ptr, "seg_ptr"), (seg_rel, "seg_rel")]
+    ops = RelOperands.build(name, row_table, col_table, G, l, WIDTHS_MFMA, idx)
+    d, n_rows, n_cols = ops.d, ops.n_rows, ops.n_cols
+    topk = int(topk)
+    if not 1 <= topk <= _lib.DG_NODE_TOPK_MAX_K:
+        raise ValueError(f"{name}: topk must be in [1, {_lib.DG_NODE_TOPK_MAX_K}]")
+    n = row_idx.numel()
+    n_seg = seg_ptr.numel() - 1
+    if n_seg < 1:
+        raise ValueError(f"{name}: seg_ptr must have n_seg + 1 >= 2 entries")
+    if seg_rel is not None and seg_rel.numel() != n_seg:
+        raise ValueError(f"{name}: seg_rel must have one entry per segment")
+    if n + 32 * n_seg >= 2**31:
+        raise ValueError(f"{name}: needs queries + 32·segments < 2^31")
+    if no_self and n_rows != n_cols:
+        raise ValueError(f"{name}: no_self needs square tables")
+    ks = set() if ops.K is None else {ops.K}  # … and the exclusion's relation count
+    ex_rowptr, ex_col = _stacked_exclusion(name, exclude, n_rows, n_cols, ks)
+    if len(ks) > 1:
+        raise ValueError(f"{name}: relation counts disagree: {sorted(ks)}")
+    K = ks.pop() if ks else None
+    if K is not None and K < 1:
+        raise ValueError(f"{name}: no relations")
+    if seg_rel is None and K is not None and n_seg > K:
+        raise ValueError(f"{name}: {n_seg} segments but {K} relations (pass seg_rel)")
+    _need_device(list(ops.tabs) + idx)
+    dev = G.device
+    if ex_rowptr is not None:
+        ex_rowptr, ex_col = _exclusion_on_device(name, ex_rowptr, ex_col, K, n_rows, dev)
+    lib = _lib.load()
+    nbytes = int(lib.dg_decoder_node_topk_workspace(n, n_seg, n_cols, topk))
+    ws = torch.empty(-(-nbytes // 16) * 2, dtype=torch.int64, device=dev) if nbytes else None
+    scores = torch.empty((n, topk), dtype=torch.float32, device=dev)
+    cols = torch.empty((n, topk), dtype=torch.int32, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    flags = (_lib.DG_NODE_TOPK_NO_SELF if no_self else 0) | (0 if column_split else _lib.DG_NODE_TOPK_NO_SPLIT)
+    check(lib.dg_decoder_node_topk_f32(*_lib.pack(
+        "dg_decoder_node_topk_f32", row_table=row_table.data_ptr(), ld_row=d, n_rows=n_rows,
+        col_table=col_table.data_ptr(), ld_col=d, n_cols=n_cols, row_idx=row_idx.data_ptr() if n else None,
+        seg_ptr=seg_ptr.data_ptr(), seg_rel=seg_rel.data_ptr() if seg_rel is not None else None, n_seg=n_seg,
+        n_queries=n, **dict(zip(("G", "g_stride", "l", "l_stride"), ops.c_args())),
+        n_rel=K if K is not None else ops.n_rel(n_seg, seg_rel is not None), d=d, topk=topk,
+        excl_rowptr=ex_rowptr.data_ptr() if ex_rowptr is not None else None,
+        excl_col=ex_col.data_ptr() if ex_col is not None else None, flags=flags,
+        out_score=scores.data_ptr() if n else None, out_col=cols.data_ptr() if n else None,
+        out_count=counts.data_ptr() if n else None, workspace=ws.data_ptr() if ws is not None else None,
+        workspace_bytes=ws.numel() * 8 if ws is not None else 0, stream=_stream_ptr(stream))),
+        "dg_decoder_node_topk_f32")
+    return scores, cols, counts
+
+
 def cross_slot_chunk(n_pairs: int, n_sel: int) -> int:
     """The slot chunk C dg_decoder_score_cross_f32 uses for n_pairs pairs against n_sel slots (one
     wave scores a 32-pair tile against C consecutive slots): the library's own choice, host only."""
