@@ -2347,6 +2347,8 @@ def dropout_rows(inp: torch.Tensor, out: torch.Tensor, state: torch.Tensor, tag:
     _dev(out, torch.float32, "out")
     _drop_state(state)
     d = inp.shape[-1]
+    if d < 1:
+        raise ValueError("dropout_rows: rows of at least one column")
     n = inp.numel() // d
     if out.numel() != inp.numel():
         raise ValueError("dropout_rows: shapes")
@@ -2387,6 +2389,8 @@ def dropout_rows_map(inp: torch.Tensor, out: torch.Tensor, rel_map: torch.Tensor
     _dev(rel_map, torch.int32, "rel_map")
     _drop_state(state)
     d = inp.shape[-1]
+    if d < 1:
+        raise ValueError("dropout_rows_map: rows of at least one column")
     n_map = rel_map.numel()
     mx = _map_max(rel_map, rel_map_max)
     if (mx + 1) * rows_per_slab >= 0xFFFFFFFF:

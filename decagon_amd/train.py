@@ -195,11 +195,25 @@ class TrainPlan:
                 drop = None
                 if fwd.drop_state is not None:  # the forward's per-relation masks of X_j's values
                     drop = (fwd.drop_state, drop_tag(1, fwd.et_index[et]), fwd.keep)
-                self._feat_specs.append(kernels.RelGroupSpec(
-                    torch.from_numpy(xt.rowptr).to(dev), torch.from_numpy(xt.col).to(dev),
-                    torch.from_numpy(xt.val).to(dev), g1, self.gW1[et], F, K, h1, n[j],
-                    vcol_max=int(xt.col.max()) if xt.nnz else -1, shared=True, drop=drop,
-                    drop_index=torch.from_numpy(perm).to(dev) if drop is not None else None))
+                xrp, xcol, xval = (torch.from_numpy(xt.rowptr).to(dev), torch.from_numpy(xt.col).to(dev),
+                                   torch.from_numpy(xt.val).to(dev))
+                vmax_x = int(xt.col.max()) if xt.nnz else -1
+                if drop is None or idmap is None:  # chunk c is relation c: mask element c·nnz + perm[p]
+                    self._feat_specs.append(kernels.RelGroupSpec(
+                        xrp, xcol, xval, g1, self.gW1[et], F, K, h1, n[j], vcol_max=vmax_x, shared=True, drop=drop,
+                        drop_index=torch.from_numpy(perm).to(dev) if drop is not None else None))
+                else:
+                    # sharded: the forward masked relation ids[c]'s copy of X_j at ids[c]·nnz (every rank
+                    # runs all K chunks), but a chunked spec would draw local chunk c at c·nnz — so one
+                    # one-chunk spec per local relation, its index carrying the global base (the kernel
+                    # adds it as uint32)
+                    if grp.K * xt.nnz >= 2**32:
+                        raise ValueError("dropout mask counter exceeds 32 bits")
+                    for c in range(K):
+                        index = (perm.astype(np.int64) + int(ids[c]) * xt.nnz).astype(np.uint32).view(np.int32)
+                        self._feat_specs.append(kernels.RelGroupSpec(
+                            xrp, xcol, xval, g1[c], self.gW1[et][c], F, 1, h1, n[j], vcol_max=vmax_x, shared=True,
+                            drop=drop, drop_index=torch.from_numpy(index).to(dev)))
             # dW2_k = H_kᵀ·dP_k with H_k = H1_j (or its per-relation dropout draw), the reduction
             # over the n_j rows split for long ones
             H = fwd.hdrop.get(et, fwd.hidden1[j])

@@ -210,7 +210,33 @@ def test_sharded_full_size_P_matches_oracle(world):
 
 
 # ---------------------------------------------------------------------------- training
-def _train_rank(rank, world, kind, split=False, dropout=0.0):
+SPARSE_F = 40  # columns of the sparse drug features of the `sparse` training case
+
+
+def _sparse_feats(g):
+    """Sparse features X_1 [n_1, SPARSE_F] for the drugs as a (coords, values, shape) tuple in CSR order
+    (rows ascending, columns ascending inside a row): 0-6 nonzeros a row, some rows empty."""
+    rng = np.random.default_rng(23)
+    n1 = g.n_nodes[1]
+    lens = rng.integers(0, 7, n1)
+    rows = np.repeat(np.arange(n1), lens)
+    cols = np.concatenate([np.sort(rng.choice(SPARSE_F, l, replace=False)) for l in lens])
+    vals = rng.uniform(0.5, 1.5, len(rows)).astype(np.float32)
+    return np.stack([rows, cols], 1).astype(np.int64), vals, (n1, SPARSE_F)
+
+
+def _train_weights(g, sparse):
+    """_weights; `sparse`: the relations out of the drugs take W1_k [SPARSE_F, 64] (X_1·W1_k, layers.py:89)."""
+    w1, w2 = _weights(g, 5)
+    if sparse:
+        rng = np.random.default_rng(29)
+        for et, K in g.edge_types.items():
+            if et[1] == 1:
+                w1[et] = rng.uniform(-0.3, 0.3, (K, SPARSE_F, 64)).astype(np.float32)
+    return w1, w2
+
+
+def _train_rank(rank, world, kind, split=False, dropout=0.0, sparse=False):
     """One sharded training step (train.py): forward (flat mode: all-reduces, and with `split`
     the proteins row-split — all-gathers), the DEDICOM decoder + hinge on a fixed batch of
     relation (1,1)_0 with given negatives, the backward (dH1 all-reduce; row-split groups'
@@ -229,15 +255,20 @@ def _train_rank(rank, world, kind, split=False, dropout=0.0):
                                     row_split_min=1000, deal_rows=[(1, 0)] if split == "deal" else ())
     else:
         shard = RelationShard.lpt(g.edge_types, nnz, rank, world, torch_allreduce())
-    w1, w2 = _weights(g, 5)
+    w1, w2 = _train_weights(g, sparse)
     W1 = LayerWeights({et: torch.from_numpy(w).to(dev) for et, w in w1.items()})
     W2 = LayerWeights({et: torch.from_numpy(w).to(dev) for et, w in w2.items()})
     dg = DeviceGraph(g.edge_types, shard.local_csr(g.csr()), dev, shard.local, row_block=shard.row_block)
+    feats = {0: None, 1: None}
+    if sparse:
+        from decagon_amd.sparse import coo_to_csr
+
+        feats[1] = coo_to_csr(*_sparse_feats(g))
     drop = None
     if dropout > 0:
         drop = (1.0 - dropout, torch.tensor([20180701, 0], dtype=torch.int64, device=dev))
-    fwd = ForwardPlan(dg, {0: None, 1: None}, W1, W2, 64, 32, shard=shard, keep_sums=True, dropout=drop)
-    tp = train.TrainPlan(fwd, W1, W2, {0: None, 1: None})
+    fwd = ForwardPlan(dg, feats, W1, W2, 64, 32, shard=shard, keep_sums=True, dropout=drop)
+    tp = train.TrainPlan(fwd, W1, W2, feats)
     R, l, rows, cols, neg = _train_batch(g)
     E = fwd.embeddings[1]
     Rt, lt = torch.from_numpy(R).to(dev), torch.from_numpy(l).to(dev)
@@ -271,7 +302,8 @@ def _train_rank(rank, world, kind, split=False, dropout=0.0):
         for et, ids in tp.local_ids.items():
             for k in ids:
                 after[name, et[0], et[1], int(k)] = st.stacks[et][int(k)].cpu().numpy()
-    info = {"row_split": sorted(shard.row_block), "dealt": sorted(shard.dealt)}
+    info = {"row_split": sorted(shard.row_block), "dealt": sorted(shard.dealt),
+            "local": {et: [int(k) for k in ids] for et, ids in tp.local_ids.items()}}
     return grads, {"R": dR.cpu().numpy(), "l": dl.cpu().numpy()}, float(hinge.loss[0]), after, info
 
 
@@ -285,11 +317,11 @@ def _train_batch(g):
     return R, l, pick[:, 0], pick[:, 1], neg
 
 
-def _train_oracle(kind, g, dropout=0.0):
+def _train_oracle(kind, g, dropout=0.0, sparse=False):
     from oracle import decagon_oracle as orc
     from test_cpu_train_oracle import _masks
 
-    w1, w2 = _weights(g, 5)
+    w1, w2 = _train_weights(g, sparse)
     R, l, rows, cols, neg = _train_batch(g)
     ets = list(g.edge_types)
     decoders = {et: "dedicom" for et in ets}
@@ -304,6 +336,12 @@ def _train_oracle(kind, g, dropout=0.0):
     feats = {t: None for t in n}
     adj = {et: [(c, v.astype(np.float32).astype(np.float64), s) for c, v, s in mats] for et, mats in g.adj.items()}
     drop1, drop2 = _masks(g.edge_types, adj, 1.0 - dropout, step=1) if dropout > 0 else (None, None)
+    if sparse:
+        feats[1] = _sparse_feats(g)
+        nnz = len(feats[1][1])
+        for gi, (et, K) in enumerate(g.edge_types.items()):
+            if et[1] == 1 and dropout > 0:  # dropout_sparse: relation k masks its copy of X_1's values
+                drop1[et] = orc.dropout_scale(20180701, 1, (1 << 16) | gi, K * nnz, 1.0 - dropout).reshape(K, nnz)
     cost, ref = orc.train_grads(g.edge_types, adj, feats,
                                 {et: [x.astype(np.float64) for x in w] for et, w in w1.items()},
                                 {et: [x.astype(np.float64) for x in w] for et, w in w2.items()},
@@ -322,14 +360,18 @@ def test_sharded_training_step_matches_oracle(kind, split, dropout):
     oracle's TF-minimize gradients (oracle.train_grads, on the same dropout masks) within 1e-4;
     a relation-sharded relation is updated by exactly one rank, a row-split group's relations
     by every rank identically (all-reduced gradients), each by one TF-Adam step (oracle.adam_tf)."""
+    _check_train(kind, split, dropout)
+
+
+def _check_train(kind, split, dropout, sparse=False):
     from oracle import decagon_oracle as orc
 
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
     world = 2
-    got = run_ranks(_train_rank, world, (kind, split, dropout))
+    got = run_ranks(_train_rank, world, (kind, split, dropout, sparse))
     g = _graph(kind)
-    cost, ref, w1, w2 = _train_oracle(kind, g, dropout)
+    cost, ref, w1, w2 = _train_oracle(kind, g, dropout, sparse)
     seen = {}
     for r in range(world):
         grads, dec, loss, after, info = got[r]
@@ -350,3 +392,15 @@ def test_sharded_training_step_matches_oracle(kind, split, dropout):
                     assert np.array_equal(seen[key], after[key]), key
                 seen[key] = after[name, i, j, k]
     assert len(seen) == 2 * sum(g.edge_types.values())  # every relation
+    return got
+
+
+def test_sharded_training_sparse_features_and_dropout():
+    """Config S on 2 ranks, relations LPT-sharded, with sparse drug features and dropout 0.1: the forward's
+    X_1·W1_k SpMM (every rank, all K global relations, chunk k masked at k·nnz) and the backward's
+    X_1ᵀ·(Â_kᵀ·dS1) SpMM over the rank's LOCAL relations must draw the same bits — those of the relation's
+    GLOBAL id.  Rank 1 owns relations 3, 4, 5 of the drug x drug group, so its local chunks are not
+    0..K_local-1.  Every gradient against oracle.train_grads on the regenerated masks within TOL."""
+    got = _check_train("S", False, 0.1, sparse=True)
+    assert any(ids and ids != list(range(len(ids))) for r in got for et, ids in got[r][4]["local"].items()
+               if et[1] == 1), "no rank holds a shifted run of feature-sourced relations"
