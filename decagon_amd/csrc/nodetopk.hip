@@ -9,13 +9,13 @@
 //   wanted row on the host, once per relation          main/Predictor/NpPredictor.py:293-313
 //
 // Form.  Launch 1: one workgroup per 32-query tile of one segment (segmap.h) and per column split.
-// It forms A = ((U ∘ l)·G) ∘ l of its 32 query rows once on v_mfma_f32_32x32x2_f32 into LDS, exactly
-// as edgerank.hip does.  The column tiles of the split are dealt to the workgroup's waves in
-// contiguous runs; a wave takes its run in blocks of 16 tiles, building first the per-row 32-bit
-// masks of permitted columns (inside the table, not excluded, not r under NO_SELF) of the whole
-// block in LDS from the sorted exclusion row, 8 entries per round trip, and then walking the tiles
-// with the next tile's rows in flight behind the current MFMAs (edgerank.hip's walk).  In place of
-// edgerank's count a wave keeps one running list of topk_list.h's keys PER QUERY ROW in LDS.  The
+// It forms A = ((U ∘ l)·G) ∘ l of its 32 query rows once on v_mfma_f32_32x32x2_f32 into LDS
+// (rank_walk.h's A block, the one topk.hip and edgerank.hip form, so that a score has the bits
+// dg_decoder_topk_f32 and dg_decoder_edge_rank_f32 give for the pair).  The waves then take
+// rank_walk.h's walk over the split's column tiles, edgerank.hip's: contiguous runs, in blocks of
+// 16 tiles whose per-row masks of permitted columns (inside the table, not excluded, not r under
+// NO_SELF) are built first.  What this file adds to the walk, in place of edgerank's count, is
+// one running list of topk_list.h's keys PER QUERY ROW that a wave keeps in LDS.  The
 // fast path is straight-line: each of a lane's 16 accumulator elements is compared with its row's
 // threshold score held in a register and masked by the row's bit; one ballot over the tile decides
 // whether the exact path runs at all.  The exact path appends the passing 64-bit keys to their
@@ -33,30 +33,22 @@
 // scores by smaller column, −0 as +0.  Keys of one query are unique and a key is only dropped
 // when topk larger ones exist, so the result is the unique top-k of the row whatever the tiling,
 // the grid or the order in which waves run.
-//
-// edgerank.hip's short routines (the half-row load, the A stripe, the masks of a block) are
-// restated here: that file's generated code is measured and pinned, and this one must form A and
-// walk the tiles with the same arithmetic so that a score has the bits dg_decoder_topk_f32 and
-// dg_decoder_edge_rank_f32 give for the pair.
 #include "common.h"
 #include "decagon_hip_ext2.h"
-#include "rel_operands.h"
-#include "segmap.h"
-#include "topk_list.h"
+#include "rank_walk.h"
 
 namespace {
 
 using dg::f32x16;
+using dg::kBlock;
 using dg::key_score;
+using dg::load_half_row;
 using dg::make_key;
 using dg::wave_lds_sync;
 
 constexpr int kMaxWaves = 4;       // waves per workgroup at most: column runs per split
 constexpr int kWaveMinTiles = 16;  // column tiles a wave of a workgroup keeps at least (one mask block)
-constexpr int kSplitGrid = 1024;   // workgroups a call wants before it stops splitting (4 per CU)
 constexpr int kSplitMinTiles = 4;  // column tiles a wave keeps at least when the columns are split
-constexpr int kBlock = 16;         // column tiles whose row masks a wave builds at once (2 KiB of LDS a wave)
-constexpr int kBatch = 8;          // exclusion entries a lane fetches per round trip
 constexpr int kMergeWaves = 4;     // queries per workgroup of the merge
 
 struct NodeTopkArgs {
@@ -88,7 +80,7 @@ inline int row_cap(int topk) {
 inline int max_waves(int cap) { return cap <= 64 ? kMaxWaves : cap <= 128 ? 2 : 1; }
 
 inline int lds_bytes(int waves, int cap, int d) {
-    return waves * 32 * cap * 8 + waves * 32 * 8 + 32 * (d + 4) * 4 + waves * kBlock * 32 * 4 + waves * 32 * 4 * 2;
+    return waves * 32 * cap * 8 + waves * 32 * 8 + 32 * dg::a_ld(d) * 4 + waves * kBlock * 32 * 4 + waves * 32 * 4 * 2;
 }
 
 struct Plan {
@@ -103,26 +95,7 @@ inline Plan plan(int64_t n_queries, int64_t n_seg, int n_cols, int topk, bool sp
     if (waves > most_w) waves = most_w;
     if (waves < 1) waves = 1;
     const int64_t n_tiles = dg::seg_tile_grid(n_queries, n_seg, 32);
-    int64_t n_split = 1;
-    if (split && n_tiles < kSplitGrid) {
-        n_split = (kSplitGrid + n_tiles - 1) / n_tiles;
-        const int64_t most = n_ct / (waves * kSplitMinTiles);
-        if (n_split > most) n_split = most;
-        if (n_split < 1) n_split = 1;
-    }
-    return Plan{waves, (int)n_split};
-}
-
-template <int H>
-__device__ __forceinline__ void load_half_row(const float* p, bool ok, float (&x)[H]) {
-#pragma unroll
-    for (int s4 = 0; s4 < H / 4; ++s4) {
-        const float4 v = ok ? *reinterpret_cast<const float4*>(p + 4 * s4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        x[4 * s4] = v.x;
-        x[4 * s4 + 1] = v.y;
-        x[4 * s4 + 2] = v.z;
-        x[4 * s4 + 3] = v.w;
-    }
+    return Plan{waves, dg::column_splits(n_tiles, n_ct, waves, kSplitMinTiles, split)};
 }
 
 // One wave's per-row lists: 32 rows of cap keys, unsorted, n[row] of them live and all above
@@ -189,7 +162,7 @@ __device__ __forceinline__ void compact_rows(const RowLists& L, uint32_t rows, i
 template <int D>
 __global__ __launch_bounds__(256) void node_topk_kernel(const NodeTopkArgs a) {
     constexpr int H = D / 2;
-    constexpr int LDA = D + 4;  // padded: 16-byte rows that do not all start on one bank
+    constexpr int LDA = dg::a_ld(D);
     extern __shared__ __attribute__((aligned(16))) unsigned char node_smem[];
 
     const int lane = threadIdx.x & 63;
@@ -208,6 +181,8 @@ __global__ __launch_bounds__(256) void node_topk_kernel(const NodeTopkArgs a) {
     uint32_t* s_mask = mask_all + w * kBlock * 32;  // this wave's row masks of one block of tiles
     RowLists L{keys_all + w * 32 * cap, thr_all + w * 32, ts_all + w * 32, n_all + w * 32, cap, topk};
 
+    // (the prologue below — tile, run, cursor — is rank_walk.h's query_tile, tile_run and
+    // excl_cursor written out: DESIGN §21, "One walk", says why)
     int s, local;
     if (!dg::seg_tile_find(a.seg_ptr, a.n_seg, 32, (int)blockIdx.x, s, local)) return;
     s = __builtin_amdgcn_readfirstlane(s);
@@ -252,31 +227,15 @@ __global__ __launch_bounds__(256) void node_topk_kernel(const NodeTopkArgs a) {
             pc = lo;
         }
     }
-    auto load_b = [&](int t, float(&x)[H]) {
-        const uint32_t col = (uint32_t)t * 32u + (uint32_t)i;
-        const bool in = t < n_ct && col < (uint32_t)a.n_cols;
-        load_half_row<H>(a.col_table + (int64_t)(in ? col : 0u) * a.ld_col + H * h, in, x);
-    };
-    float b[H], bn[H];
-    load_b(t0 < t1 ? t0 : n_ct, b);
+    float b[H];
+    dg::load_col_tile<H>(a.col_table, a.ld_col, a.n_cols, n_ct, t0 < t1 ? t0 : n_ct, i, h, b);
 
-    // A = ((U ∘ l)·G) ∘ l of the 32 query rows, 32 columns at a time (edgerank.hip's stripe)
+    // A of the 32 query rows, 32 columns at a time
     if (w < D / 32) {  // (the waves that form a block of the stripe)
         float u[H];
         load_half_row<H>(a.row_table + (int64_t)r * a.ld_row + H * h, ok, u);
 #pragma unroll 1
-        for (int nb = w; nb < D / 32; nb += W) {
-            f32x16 acc = {};
-#pragma unroll
-            for (int t = 0; t < H; ++t) {
-                const int kk = H * h + t;
-                const float av = l ? u[t] * l[kk] : u[t];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, G[kk * D + nb * 32 + i], acc, 0, 0, 0);
-            }
-            const float lj = l ? l[nb * 32 + i] : 1.0f;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) As[dg::acc_row(q, h) * LDA + nb * 32 + i] = acc[q] * lj;
-        }
+        for (int nb = w; nb < D / 32; nb += W) dg::a_block<D>(u, G, l, nb, i, h, As);
     }
     if (h == 0) {
         L.n[i] = 0;
@@ -293,56 +252,25 @@ __global__ __launch_bounds__(256) void node_topk_kernel(const NodeTopkArgs a) {
     for (int q = 0; q < 16; ++q) ts[q] = -__builtin_inff();
 
     const bool no_self = (a.flags & DG_NODE_TOPK_NO_SELF) != 0;
+    float bn[H];
 #pragma unroll 1
     for (int tb = t0; tb < t1; tb += kBlock) {  // the run in blocks of kBlock tiles: masks first, then the walk
         const int nt = t1 - tb < kBlock ? t1 - tb : kBlock;
         wave_lds_sync();  // the previous block's masks have been read
-        if (h == 0) {
-            // row i's permitted columns of every tile of the block, before the exclusion ...
-#pragma unroll 1
-            for (int t = 0; t < nt; ++t) {
-                const int ct = tb + t;
-                const uint32_t left = (uint32_t)a.n_cols - (uint32_t)ct * 32u;  // ≥ 1: columns from the tile's first on
-                uint32_t m = left >= 32u ? ~0u : (1u << left) - 1u;
-                if (no_self && (r >> 5) == ct) m &= ~(1u << (r & 31));
-                s_mask[t * 32 + i] = ok ? m : 0u;
-            }
-            // ... and without the excluded ones: kBatch entries of the sorted row per round trip,
-            // until one lies past the block
-            bool more = pc < pe;
-            while (more) {
-                int e[kBatch];
-#pragma unroll
-                for (int j = 0; j < kBatch; ++j) e[j] = a.ex_col[pc + j < pe ? pc + j : pe - 1];
-                int used = 0;
-#pragma unroll
-                for (int j = 0; j < kBatch; ++j) {
-                    const int t = (e[j] >> 5) - tb;
-                    const bool live = pc + j < pe && t < nt;
-                    if (live && t >= 0) atomicAnd(&s_mask[t * 32 + i], ~(1u << (e[j] & 31)));
-                    used += live;
-                }
-                pc += used;
-                more = used == kBatch && pc < pe;
-            }
-        }
+        if (h == 0)
+            dg::build_masks(s_mask, i, tb, nt, a.n_cols, a.ex_col, pc, pe, [&](int ct, uint32_t m) {
+                if (no_self && (r >> 5) == ct) m &= ~(1u << (r & 31));  // not r under NO_SELF
+                return ok ? m : 0u;                                      // nothing of a query outside the table
+            });
         wave_lds_sync();
 #pragma unroll 1
         for (int t = 0; t < nt; ++t) {
             const int ct = tb + t;
-            load_b(ct + 1 < t1 ? ct + 1 : n_ct, bn);  // next tile's rows in flight behind this tile's MFMAs
-            f32x16 acc = {};
-#pragma unroll
-            for (int u = 0; u < H; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[u], b[u], acc, 0, 0, 0);
-            uint32_t mr[16];  // mr[q]: the mask of tile row acc_row(q, h) = (q & 3) + 8·(q >> 2) + 4·h
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const uint4 v = *reinterpret_cast<const uint4*>(&s_mask[t * 32 + 8 * g + 4 * h]);
-                mr[4 * g] = v.x;
-                mr[4 * g + 1] = v.y;
-                mr[4 * g + 2] = v.z;
-                mr[4 * g + 3] = v.w;
-            }
+            // next tile's rows in flight behind this tile's MFMAs
+            dg::load_col_tile<H>(a.col_table, a.ld_col, a.n_cols, n_ct, ct + 1 < t1 ? ct + 1 : n_ct, i, h, bn);
+            const f32x16 acc = dg::tile_scores<H>(af, b);
+            uint32_t mr[16];
+            dg::row_masks(s_mask + t * 32, h, mr);
             // the fast path: does any element reach its row's threshold?  (−0 == +0 in fp32 and a
             // list's threshold is never above its topk-th key, so this admits a superset)
             bool any = false;
@@ -473,23 +401,16 @@ extern "C" int dg_decoder_node_topk_f32(const float* row_table, int64_t ld_row, 
                                         const int32_t* excl_rowptr, const int32_t* excl_col, int32_t flags,
                                         float* out_score, int32_t* out_col, int32_t* out_count, void* workspace,
                                         int64_t workspace_bytes, void* stream) {
-    if (n_seg <= 0 || n_queries < 0 || (d != 32 && d != 64)) return DG_EINVAL;
-    if (!row_table || !col_table || !seg_ptr || !G) return DG_EINVAL;
-    if (n_queries > 0 && (!row_idx || !out_score || !out_col || !out_count)) return DG_EINVAL;
-    if (n_rows < 1 || n_cols < 1 || ld_row < d || ld_col < d) return DG_EINVAL;
+    if (n_queries > 0 && (!out_score || !out_col || !out_count)) return DG_EINVAL;
     if (topk < 1 || topk > DG_NODE_TOPK_MAX_K) return DG_EINVAL;
-    NodeTopkArgs a{};
-    if (dg::rel_ops(G, g_stride, l, l_stride, n_rel, d, seg_rel != nullptr, n_seg, a.ops) != DG_OK) return DG_EINVAL;
-    if ((excl_rowptr == nullptr) != (excl_col == nullptr)) return DG_EINVAL;
-    if (excl_rowptr && !seg_rel && n_seg > n_rel) return DG_EINVAL;  // segment s reads exclusion relation s
-    if (flags & ~(DG_NODE_TOPK_NO_SELF | DG_NODE_TOPK_NO_SPLIT)) return DG_EINVAL;
-    if ((flags & DG_NODE_TOPK_NO_SELF) && n_rows != n_cols) return DG_EINVAL;
-    if ((int64_t)n_queries + 32LL * n_seg >= (1ll << 31)) return DG_EINVAL;  // 32-bit query offsets
     const int64_t need = dg_decoder_node_topk_workspace(n_queries, n_seg, n_cols, topk);
     if (workspace_bytes < need || (need > 0 && !workspace)) return DG_EINVAL;
-    if (!dg::aligned16(row_table) || !dg::aligned16(col_table) || (ld_row & 3) || (ld_col & 3) ||
-        (need > 0 && !dg::aligned16(workspace)))
-        return DG_EALIGN;
+    NodeTopkArgs a{};
+    const int rc0 = dg::check_rank_call(row_table, ld_row, n_rows, col_table, ld_col, n_cols, row_idx, seg_ptr, seg_rel,
+                                        n_seg, n_queries, G, g_stride, l, l_stride, n_rel, d, excl_rowptr, excl_col,
+                                        flags, DG_NODE_TOPK_NO_SELF, DG_NODE_TOPK_NO_SPLIT, a.ops);
+    if (rc0 != DG_OK) return rc0;
+    if (need > 0 && !dg::aligned16(workspace)) return DG_EALIGN;
     if (n_queries == 0) return DG_OK;
 
     const Plan pl = plan(n_queries, n_seg, n_cols, topk, !(flags & DG_NODE_TOPK_NO_SPLIT));

@@ -1,5 +1,6 @@
 // The per-relation decoder operands of the "every relation of an edge type in one pass" entry
-// points (evalseg.hip, gradseg.hip, profile.hip, topk.hip) — include/decagon_hip.h,
+// points (evalseg.hip, gradseg.hip, profile.hip, topk.hip, and through rank_walk.h edgerank.hip
+// and nodetopk.hip) — include/decagon_hip.h,
 // "Per-relation operands":
 //   G is [d, d] shared by every relation (g_stride 0) or [K, d, d] (g_stride d·d);
 //   l is absent, [d] (l_stride 0) or [K, d] (l_stride d);

@@ -22,13 +22,18 @@
 // Keys are unique, and a key is only ever dropped when topk larger keys of the same relation
 // exist, so the result is the unique top-k of the relation whatever the tiling, the grid or
 // the order in which waves run.
+//
+// The half-row load, the A block and the tile product are rank_walk.h's, shared with edgerank.hip
+// and nodetopk.hip (a pair's score has the same bits from all three).  The walk itself is this
+// file's own: one dependent exclusion load per entry beside each tile and one list per wave — the
+// later kernels left it for rank_walk.h's masks.
 #include "common.h"
-#include "rel_operands.h"
-#include "topk_list.h"
+#include "rank_walk.h"
 
 namespace {
 
 using dg::f32x16;
+using dg::load_half_row;
 
 constexpr int kStripe = 128;  // rows per workgroup: one 32-row block per wave
 constexpr int kWaves = 4;    // waves per workgroup = candidate lists per stripe
@@ -50,24 +55,10 @@ struct TopkArgs {
     int32_t n_rows, n_cols, n_stripes, topk, cap, flags;
 };
 
-template <int H>
-__device__ __forceinline__ void load_half_row(const float* p, bool ok, float (&x)[H]) {
-#pragma unroll
-    for (int s4 = 0; s4 < H / 4; ++s4) {
-        const float4 v = ok ? *reinterpret_cast<const float4*>(p + 4 * s4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        x[4 * s4] = v.x;
-        x[4 * s4 + 1] = v.y;
-        x[4 * s4 + 2] = v.z;
-        x[4 * s4 + 3] = v.w;
-    }
-}
-
-// MFMA s of a 32×32 tile takes k = H·h + s from lane half h (the contraction order is free as
-// long as A and B agree), so each lane's operands are H = D/2 contiguous floats of its row.
 template <int D>
 __global__ __launch_bounds__(256) void topk_stripe_kernel(TopkArgs a) {
     constexpr int H = D / 2;
-    constexpr int LDA = D + 4;  // padded: 16-byte rows that do not all start on one bank
+    constexpr int LDA = dg::a_ld(D);
     extern __shared__ __attribute__((aligned(16))) unsigned char topk_smem[];
     float* As = reinterpret_cast<float*>(topk_smem);  // [kStripe][LDA]
     uint64_t* bufs = reinterpret_cast<uint64_t*>(topk_smem + kStripe * LDA * sizeof(float));
@@ -79,8 +70,7 @@ __global__ __launch_bounds__(256) void topk_stripe_kernel(TopkArgs a) {
     const float* G = a.G + (int64_t)rel * a.g_stride;
     const float* l = a.l ? a.l + (int64_t)rel * a.l_stride : nullptr;
 
-    // A = ((U ∘ l)·G) ∘ l: wave w forms its own 32 rows, 32 columns at a time.  (Through LDS: the
-    // MFMA leaves a row's 32 columns on 32 lanes, the next product wants them in one lane.)
+    // A = ((U ∘ l)·G) ∘ l: wave w forms its own 32 rows, 32 columns at a time
     const int rb = w;
     {
         const int row = r0 + rb * 32 + i;
@@ -88,21 +78,7 @@ __global__ __launch_bounds__(256) void topk_stripe_kernel(TopkArgs a) {
         float u[H];
         load_half_row<H>(a.row_table + (int64_t)(ok ? row : 0) * a.ld_row + H * h, ok, u);
 #pragma unroll
-        for (int nb = 0; nb < D / 32; ++nb) {
-            f32x16 acc = {};
-#pragma unroll
-            for (int s = 0; s < H; ++s) {
-                const int k = H * h + s;
-                const float av = l ? u[s] * l[k] : u[s];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, G[k * D + nb * 32 + i], acc, 0, 0, 0);
-            }
-            const float lj = l ? l[nb * 32 + i] : 1.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rl = dg::acc_row(r, h);
-                As[(rb * 32 + rl) * LDA + nb * 32 + i] = acc[r] * lj;
-            }
-        }
+        for (int nb = 0; nb < D / 32; ++nb) dg::a_block<D>(u, G, l, nb, i, h, As + rb * 32 * LDA);
     }
     __syncthreads();
 
@@ -138,9 +114,7 @@ __global__ __launch_bounds__(256) void topk_stripe_kernel(TopkArgs a) {
 #pragma unroll 1
     for (; ct < n_ct; ++ct) {
         load_b(ct + 1, bn);  // next tile's rows in flight behind this tile's MFMAs
-        f32x16 acc = {};
-#pragma unroll
-        for (int s = 0; s < H; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s], b[s], acc, 0, 0, 0);
+        const f32x16 acc = dg::tile_scores<H>(af, b);
         const int c0 = ct * 32, c = c0 + i;
         uint32_t ex = 0;  // excluded columns of row myrow inside this tile
         while (p < pe) {

@@ -1,5 +1,6 @@
 // One wave's running top-k list in LDS and its total-order 64-bit keys, shared by topk.hip (the
-// best pairs of every relation) and profile.hip (the best columns of every row).
+// best pairs of every relation), profile.hip (the best columns of every row) and nodetopk.hip (the
+// keys of its per-row lists, WaveTopK in its merge); rank_walk.h takes wave_lds_sync from here.
 //
 // A candidate is one key, (monotone map of the score's bits) << 32 | ~index: unsigned comparison
 // orders by higher score, then smaller index (−0 is made +0 first).  Keys are unique, and a key is

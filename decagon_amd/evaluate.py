@@ -537,6 +537,66 @@ def top_relations(sess, opt, placeholders, feed_dict, pairs, edge_type_ij, k: in
 RANK_SIDES = ("col", "row", "both")
 
 
+def _side_query(name, sess, opt, placeholders, feed_dict, edge_type_ij, *, exclude, side, sigmoid, pack, call,
+                own_checks=None):
+    """The part edge_ranks and top_partners share: (packed, sides, flat).  Checks the side, the edge
+    type and `sigmoid`, refuses a sharded session and a fed latent; then one sess.run at dropout 0
+    of a Node that packs the query on the host — pack(K, shape) gives (queries, seg_ptr, relations,
+    packed): the per-query index arrays (the row table's first), and what the result dictionary
+    opens with — uploads [queries | seg_ptr | relations] once, and for every side returns the
+    tensors of call(row_t, col_t, queries, seg_ptr, G, l, relations, exclude), all concatenated as
+    int32 for one copy back.  Side "row" is the same call with the tables and the queries swapped,
+    G transposed per relation and the exclusion transposed: `queries` is (row-table index,
+    column-table index) for a query that is a pair — so it is reversed with the tables — or one
+    array for a query that is a node of whichever table is the row table.  `own_checks()` raises
+    the caller's own ValueErrors where they always stood: after the edge type's."""
+    from .graph import InvalidArgumentError
+    from .sparse import exclusion_csr
+
+    if side not in RANK_SIDES:
+        raise ValueError(f"side must be one of {list(RANK_SIDES)}")
+    model = opt._model()
+    _edge_type_decoder(model, edge_type_ij, sigmoid)
+    if own_checks is not None:
+        own_checks()
+    if getattr(sess, "shard", None) is not None:
+        raise NotImplementedError(f"{name} runs on one GPU (the session is sharded)")
+    et = tuple(edge_type_ij)
+    sides = ("col", "row") if side == "both" else (side,)
+    fd = dict(feed_dict)
+    fd[placeholders["dropout"]] = 0.0
+    packed = {}
+
+    def fn(ctx: RunContext):
+        if latent_fed(ctx, opt, model, et):
+            raise InvalidArgumentError(f"{name} reads the decoder's variables; a latent matrix is fed")
+        K, row_t, col_t, G, l = _edge_type_operands(name, ctx, opt, model, et)
+        shape = (row_t.shape[0], col_t.shape[0])
+        queries, seg_ptr, rels, head = pack(K, shape)
+        packed.update(head)
+        ex = exclude
+        if ex is not None and not hasattr(ex, "rowptr"):
+            ex = exclusion_csr(ex, shape)
+        if ex is not None and (int(ex.n_rels), int(ex.n_rows), int(ex.n_cols)) != (K,) + shape:
+            raise ValueError(f"{name}: exclusion of {ex.n_rels} relations, {ex.n_rows} × {ex.n_cols}; "
+                             f"the edge type has {K}, {shape[0]} × {shape[1]}")
+        n, n_seg = queries[0].size, rels.size
+        buf = torch.from_numpy(np.concatenate([*queries, seg_ptr, rels]).astype(np.int32)).to(ctx.session.device)
+        d_q = [buf[n * t:n * (t + 1)] for t in range(len(queries))]
+        d_seg, d_rel = buf[n * len(d_q):n * len(d_q) + n_seg + 1], buf[n * len(d_q) + n_seg + 1:]
+        out = []
+        for sd in sides:
+            if sd == "col":
+                out += call(row_t, col_t, d_q, d_seg, G, l, d_rel, ex)
+            else:
+                out += call(col_t, row_t, d_q[::-1], d_seg, G.transpose(-1, -2).contiguous(), l, d_rel,
+                            ex.transposed() if ex is not None else None)
+        return torch.cat([t.view(torch.int32).reshape(-1) for t in out])  # one copy back
+
+    flat = np.asarray(sess.run(Node(f"evaluate/{name}", fn), feed_dict=fd), np.int32)
+    return packed, sides, flat
+
+
 def edge_ranks(sess, opt, placeholders, feed_dict, edges, edge_type_ij, relations=None, exclude=None,
                side: str = "col", no_self: bool = False) -> dict:
     """The filtered rank of held-out edges of edge type (i, j) — "given drug u and side effect k,
@@ -563,53 +623,16 @@ def edge_ranks(sess, opt, placeholders, feed_dict, edges, edge_type_ij, relation
     Returns {"relations": int32 [n_sel], "seg_ptr": int32 [n_sel + 1], and per side ("col" / "row")
     {"rank": int32 [n], "cand": int32 [n], "score": float32 [n]}}: query q of relation relations[s]
     lies in [seg_ptr[s], seg_ptr[s+1]), in the order of `edges`; 1 <= rank <= cand."""
-    from .graph import InvalidArgumentError
-    from .sparse import exclusion_csr
+    def pack(K, shape):
+        ri, ci, seg_ptr, _, rels = pack_edge_samples(edges, {}, tuple(edge_type_ij), K, shape, relations)
+        return [ri, ci], seg_ptr, rels, {"relations": rels, "seg_ptr": seg_ptr}
 
-    if side not in RANK_SIDES:
-        raise ValueError(f"side must be one of {list(RANK_SIDES)}")
-    model = opt._model()
-    _edge_type_decoder(model, edge_type_ij, None)
-    if getattr(sess, "shard", None) is not None:
-        raise NotImplementedError("edge_ranks runs on one GPU (the session is sharded)")
-    et = tuple(edge_type_ij)
-    sides = ("col", "row") if side == "both" else (side,)
-    fd = dict(feed_dict)
-    fd[placeholders["dropout"]] = 0.0
-    packed = {}
+    def call(row_t, col_t, q, seg, G, l, rel, ex):
+        return kernels.decoder_edge_rank(row_t, col_t, q[0], q[1], seg, G, l, seg_rel=rel, exclude=ex, no_self=no_self)
 
-    def fn(ctx: RunContext):
-        if latent_fed(ctx, opt, model, et):
-            raise InvalidArgumentError("edge_ranks reads the decoder's variables; a latent matrix is fed")
-        K, row_t, col_t, G, l = _edge_type_operands("edge_ranks", ctx, opt, model, et)
-        shape = (row_t.shape[0], col_t.shape[0])
-        ri, ci, seg_ptr, _, rels = pack_edge_samples(edges, {}, et, K, shape, relations)
-        packed["relations"], packed["seg_ptr"] = rels, seg_ptr
-        ex = exclude
-        if ex is not None and not hasattr(ex, "rowptr"):
-            ex = exclusion_csr(ex, shape)
-        if ex is not None and (int(ex.n_rels), int(ex.n_rows), int(ex.n_cols)) != (K,) + shape:
-            raise ValueError(f"edge_ranks: exclusion of {ex.n_rels} relations, {ex.n_rows} × {ex.n_cols}; "
-                             f"the edge type has {K}, {shape[0]} × {shape[1]}")
-        n, n_seg = ri.size, rels.size
-        buf = torch.from_numpy(np.concatenate([ri, ci, seg_ptr, rels]).astype(np.int32)).to(ctx.session.device)
-        d_ri, d_ci, d_seg, d_rel = buf[:n], buf[n:2 * n], buf[2 * n:2 * n + n_seg + 1], buf[2 * n + n_seg + 1:]
-        out = []
-        for sd in sides:
-            if sd == "col":
-                res = kernels.decoder_edge_rank(row_t, col_t, d_ri, d_ci, d_seg, G, l, seg_rel=d_rel, exclude=ex,
-                                                no_self=no_self)
-            else:
-                res = kernels.decoder_edge_rank(col_t, row_t, d_ci, d_ri, d_seg, G.transpose(-1, -2).contiguous(), l,
-                                                seg_rel=d_rel, exclude=ex.transposed() if ex is not None else None,
-                                                no_self=no_self)
-            rank, score, cand = res
-            out += [rank, score.view(torch.int32), cand]
-        return torch.cat(out)  # one copy back
-
-    flat = np.asarray(sess.run(Node("evaluate/edge_ranks", fn), feed_dict=fd), np.int32)
+    res, sides, flat = _side_query("edge_ranks", sess, opt, placeholders, feed_dict, edge_type_ij, exclude=exclude,
+                                   side=side, sigmoid=None, pack=pack, call=call)
     n = flat.size // (3 * len(sides))
-    res = dict(packed)
     for t, sd in enumerate(sides):
         part = flat[3 * n * t:3 * n * (t + 1)]
         res[sd] = {"rank": part[:n].copy(), "score": part[n:2 * n].view(np.float32).copy(), "cand": part[2 * n:].copy()}
@@ -685,57 +708,22 @@ def top_partners(sess, opt, placeholders, feed_dict, nodes, edge_type_ij, k: int
     side ("col" / "row") {"partner": int32 [n, k], "score": [n, k], "count": int32 [n]}}: query q
     of relation relations[s] lies in [seg_ptr[s], seg_ptr[s+1]), in the order of `nodes`;
     count = min(k, permitted partners), slots past it hold −1 / −inf."""
-    from .graph import InvalidArgumentError
-    from .sparse import exclusion_csr
+    def k_in_range():
+        if not 1 <= int(k) <= _lib.DG_NODE_TOPK_MAX_K:
+            raise ValueError(f"top_partners: k must be in [1, {_lib.DG_NODE_TOPK_MAX_K}]")
 
-    if side not in RANK_SIDES:
-        raise ValueError(f"side must be one of {list(RANK_SIDES)}")
-    model = opt._model()
-    _edge_type_decoder(model, edge_type_ij, sigmoid)
-    k = int(k)
-    if not 1 <= k <= _lib.DG_NODE_TOPK_MAX_K:
-        raise ValueError(f"top_partners: k must be in [1, {_lib.DG_NODE_TOPK_MAX_K}]")
-    if getattr(sess, "shard", None) is not None:
-        raise NotImplementedError("top_partners runs on one GPU (the session is sharded)")
-    et = tuple(edge_type_ij)
-    sides = ("col", "row") if side == "both" else (side,)
-    fd = dict(feed_dict)
-    fd[placeholders["dropout"]] = 0.0
-    packed = {}
-
-    def fn(ctx: RunContext):
-        if latent_fed(ctx, opt, model, et):
-            raise InvalidArgumentError("top_partners reads the decoder's variables; a latent matrix is fed")
-        K, row_t, col_t, G, l = _edge_type_operands("top_partners", ctx, opt, model, et)
-        shape = (row_t.shape[0], col_t.shape[0])
+    def pack(K, shape):
         n_nodes = min(shape) if side == "both" else shape[0] if side == "col" else shape[1]
         idx, seg_ptr, rels = pack_node_queries(nodes, K, n_nodes, relations)
-        packed["relations"], packed["seg_ptr"], packed["nodes"] = rels, seg_ptr, idx
-        ex = exclude
-        if ex is not None and not hasattr(ex, "rowptr"):
-            ex = exclusion_csr(ex, shape)
-        if ex is not None and (int(ex.n_rels), int(ex.n_rows), int(ex.n_cols)) != (K,) + shape:
-            raise ValueError(f"top_partners: exclusion of {ex.n_rels} relations, {ex.n_rows} × {ex.n_cols}; "
-                             f"the edge type has {K}, {shape[0]} × {shape[1]}")
-        n, n_seg = idx.size, rels.size
-        buf = torch.from_numpy(np.concatenate([idx, seg_ptr, rels]).astype(np.int32)).to(ctx.session.device)
-        d_idx, d_seg, d_rel = buf[:n], buf[n:n + n_seg + 1], buf[n + n_seg + 1:]
-        out = []
-        for sd in sides:
-            if sd == "col":
-                res = kernels.decoder_node_topk(row_t, col_t, d_idx, d_seg, G, l, k, seg_rel=d_rel, exclude=ex,
-                                                no_self=no_self)
-            else:
-                res = kernels.decoder_node_topk(col_t, row_t, d_idx, d_seg, G.transpose(-1, -2).contiguous(), l, k,
-                                                seg_rel=d_rel, exclude=ex.transposed() if ex is not None else None,
-                                                no_self=no_self)
-            score, col, count = res
-            out += [score.view(torch.int32).reshape(-1), col.reshape(-1), count]
-        return torch.cat(out)  # one copy back
+        return [idx], seg_ptr, rels, {"relations": rels, "seg_ptr": seg_ptr, "nodes": idx}
 
-    flat = np.asarray(sess.run(Node("evaluate/top_partners", fn), feed_dict=fd), np.int32)
+    def call(row_t, col_t, q, seg, G, l, rel, ex):
+        return kernels.decoder_node_topk(row_t, col_t, q[0], seg, G, l, k, seg_rel=rel, exclude=ex, no_self=no_self)
+
+    res, sides, flat = _side_query("top_partners", sess, opt, placeholders, feed_dict, edge_type_ij, exclude=exclude,
+                                   side=side, sigmoid=sigmoid, pack=pack, call=call, own_checks=k_in_range)
+    k = int(k)
     n = flat.size // ((2 * k + 1) * len(sides))
-    res = dict(packed)
     for t, sd in enumerate(sides):
         part = flat[(2 * k + 1) * n * t:(2 * k + 1) * n * (t + 1)]
         s = part[:n * k].view(np.float32).reshape(n, k).copy()

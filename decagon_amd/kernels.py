@@ -1279,6 +1279,51 @@ def _exclusion_on_device(name, ex_rowptr, ex_col, K: int, n_rows: int, dev):
     return ex_rowptr, ex_col
 
 
+def _relation_count(name, ops: RelOperands, exclude):
+    """(K, ex_rowptr, ex_col): the relation count the operands and `exclude` agree on (None where
+    nothing is per relation) and _stacked_exclusion's pair."""
+    ks = set() if ops.K is None else {ops.K}  # … and the exclusion's relation count
+    ex_rowptr, ex_col = _stacked_exclusion(name, exclude, ops.n_rows, ops.n_cols, ks)
+    if len(ks) > 1:
+        raise ValueError(f"{name}: relation counts disagree: {sorted(ks)}")
+    K = ks.pop() if ks else None
+    if K is not None and K < 1:
+        raise ValueError(f"{name}: no relations")
+    return K, ex_rowptr, ex_col
+
+
+def _segmented_ranking(name, row_table, col_table, G, l, queries, seg_ptr, seg_rel, exclude, no_self: bool,
+                       own_checks=None):
+    """The preparation decoder_edge_rank and decoder_node_topk share: (ops, n, n_seg, n_rel,
+    ex_rowptr, ex_col).  `queries` are the (tensor, name) pairs of the per-query index tensors, n
+    their common length.  Checks the operands, the segments, the 2^31 bound, no_self and the
+    relation counts, then that everything is on the device, and puts the exclusion there.
+    `own_checks()` raises the caller's own ValueErrors where they always stood: after the operands'."""
+    idx = list(queries) + [(seg_ptr, "seg_ptr"), (seg_rel, "seg_rel")]
+    ops = RelOperands.build(name, row_table, col_table, G, l, WIDTHS_MFMA, idx)
+    if own_checks is not None:
+        own_checks()
+    n = queries[0][0].numel()
+    if any(t.numel() != n for t, _ in queries):
+        raise ValueError(f"{name}: {' / '.join(nm for _, nm in queries)} length mismatch")
+    n_seg = seg_ptr.numel() - 1
+    if n_seg < 1:
+        raise ValueError(f"{name}: seg_ptr must have n_seg + 1 >= 2 entries")
+    if seg_rel is not None and seg_rel.numel() != n_seg:
+        raise ValueError(f"{name}: seg_rel must have one entry per segment")
+    if n + 32 * n_seg >= 2**31:
+        raise ValueError(f"{name}: needs queries + 32·segments < 2^31")
+    if no_self and ops.n_rows != ops.n_cols:
+        raise ValueError(f"{name}: no_self needs square tables")
+    K, ex_rowptr, ex_col = _relation_count(name, ops, exclude)
+    if seg_rel is None and K is not None and n_seg > K:
+        raise ValueError(f"{name}: {n_seg} segments but {K} relations (pass seg_rel)")
+    _need_device(list(ops.tabs) + idx)
+    ex_rowptr, ex_col = _exclusion_on_device(name, ex_rowptr, ex_col, K, ops.n_rows, G.device)
+    n_rel = K if K is not None else ops.n_rel(n_seg, seg_rel is not None)
+    return ops, n, n_seg, n_rel, ex_rowptr, ex_col
+
+
 def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tensor, l: Optional[torch.Tensor],
                  topk: int, exclude=None, upper: bool = False, no_diag: bool = False, stream=None
                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -1302,13 +1347,8 @@ def decoder_topk(row_table: torch.Tensor, col_table: torch.Tensor, G: torch.Tens
         raise ValueError("decoder_topk: needs 1 <= N_i·N_j < 2^32")
     if upper and n_rows != n_cols:
         raise ValueError("decoder_topk: upper needs square tables")
-    ks = set() if ops.K is None else {ops.K}  # … and the exclusion's relation count
-    ex_rowptr, ex_col = _stacked_exclusion("decoder_topk", exclude, n_rows, n_cols, ks)
-    if len(ks) > 1:
-        raise ValueError(f"decoder_topk: relation counts disagree: {sorted(ks)}")
-    K = ks.pop() if ks else 1
-    if K < 1:
-        raise ValueError("decoder_topk: no relations")
+    K, ex_rowptr, ex_col = _relation_count("decoder_topk", ops, exclude)
+    K = 1 if K is None else K
     _need_device(ops.tabs)
     dev = G.device
     ex_rowptr, ex_col = _exclusion_on_device("decoder_topk", ex_rowptr, ex_col, K, n_rows, dev)
@@ -1348,35 +1388,10 @@ def decoder_edge_rank(row_table: torch.Tensor, col_table: torch.Tensor, row_idx:
     sparse.ExclusionCSR (uploaded here) or a device (rowptr, col) pair; its relation count is K too.
     column_split=False keeps every query tile's columns in one workgroup (the measured alternative
     of DESIGN.md §20; same results)."""
-    name = "decoder_edge_rank"
-    idx = [(row_idx, "row_idx"), (col_idx, "col_idx"), (seg_ptr, "seg_ptr"), (seg_rel, "seg_rel")]
-    ops = RelOperands.build(name, row_table, col_table, G, l, WIDTHS_MFMA, idx)
-    d, n_rows, n_cols = ops.d, ops.n_rows, ops.n_cols
-    n = row_idx.numel()
-    if col_idx.numel() != n:
-        raise ValueError(f"{name}: row_idx / col_idx length mismatch")
-    n_seg = seg_ptr.numel() - 1
-    if n_seg < 1:
-        raise ValueError(f"{name}: seg_ptr must have n_seg + 1 >= 2 entries")
-    if seg_rel is not None and seg_rel.numel() != n_seg:
-        raise ValueError(f"{name}: seg_rel must have one entry per segment")
-    if n + 32 * n_seg >= 2**31:
-        raise ValueError(f"{name}: needs queries + 32·segments < 2^31")
-    if no_self and n_rows != n_cols:
-        raise ValueError(f"{name}: no_self needs square tables")
-    ks = set() if ops.K is None else {ops.K}  # … and the exclusion's relation count
-    ex_rowptr, ex_col = _stacked_exclusion(name, exclude, n_rows, n_cols, ks)
-    if len(ks) > 1:
-        raise ValueError(f"{name}: relation counts disagree: {sorted(ks)}")
-    K = ks.pop() if ks else None
-    if K is not None and K < 1:
-        raise ValueError(f"{name}: no relations")
-    if seg_rel is None and K is not None and n_seg > K:
-        raise ValueError(f"{name}: {n_seg} segments but {K} relations (pass seg_rel)")
-    _need_device(list(ops.tabs) + idx)
-    dev = G.device
-    if ex_rowptr is not None:
-        ex_rowptr, ex_col = _exclusion_on_device(name, ex_rowptr, ex_col, K, n_rows, dev)
+    ops, n, n_seg, n_rel, ex_rowptr, ex_col = _segmented_ranking(
+        "decoder_edge_rank", row_table, col_table, G, l, [(row_idx, "row_idx"), (col_idx, "col_idx")], seg_ptr,
+        seg_rel, exclude, no_self)
+    d, n_rows, n_cols, dev = ops.d, ops.n_rows, ops.n_cols, G.device
     rank = torch.empty(n, dtype=torch.int32, device=dev)
     score = torch.empty(n, dtype=torch.float32, device=dev)
     cand = torch.empty(n, dtype=torch.int32, device=dev)
@@ -1388,8 +1403,7 @@ def decoder_edge_rank(row_table: torch.Tensor, col_table: torch.Tensor, row_idx:
         col_idx=col_idx.data_ptr() if n else None, seg_ptr=seg_ptr.data_ptr(),
         seg_rel=seg_rel.data_ptr() if seg_rel is not None else None, n_seg=n_seg, n_queries=n,
         **dict(zip(("G", "g_stride", "l", "l_stride"), ops.c_args())),
-        n_rel=K if K is not None else ops.n_rel(n_seg, seg_rel is not None), d=d,
-        excl_rowptr=ex_rowptr.data_ptr() if ex_rowptr is not None else None,
+        n_rel=n_rel, d=d, excl_rowptr=ex_rowptr.data_ptr() if ex_rowptr is not None else None,
         excl_col=ex_col.data_ptr() if ex_col is not None else None, flags=flags,
         out_rank=rank.data_ptr() if n else None, out_score=score.data_ptr() if n else None,
         out_cand=cand.data_ptr() if n else None, stream=_stream_ptr(stream))), "dg_decoder_edge_rank_f32")
@@ -1414,36 +1428,15 @@ def decoder_node_topk(row_table: torch.Tensor, col_table: torch.Tensor, row_idx:
     G, l, seg_rel, exclude: as decoder_edge_rank (d is 32 or 64).  column_split=False keeps every
     query tile's columns in one workgroup (the measured alternative of DESIGN.md §21; same
     results)."""
-    name = "decoder_node_topk"
-    idx = [(row_idx, "row_idx"), (seg_ptr, "seg_ptr"), (seg_rel, "seg_rel")]
-    ops = RelOperands.build(name, row_table, col_table, G, l, WIDTHS_MFMA, idx)
-    d, n_rows, n_cols = ops.d, ops.n_rows, ops.n_cols
+    def topk_in_range():
+        if not 1 <= int(topk) <= _lib.DG_NODE_TOPK_MAX_K:
+            raise ValueError(f"decoder_node_topk: topk must be in [1, {_lib.DG_NODE_TOPK_MAX_K}]")
+
+    ops, n, n_seg, n_rel, ex_rowptr, ex_col = _segmented_ranking(
+        "decoder_node_topk", row_table, col_table, G, l, [(row_idx, "row_idx")], seg_ptr, seg_rel, exclude, no_self,
+        own_checks=topk_in_range)
     topk = int(topk)
-    if not 1 <= topk <= _lib.DG_NODE_TOPK_MAX_K:
-        raise ValueError(f"{name}: topk must be in [1, {_lib.DG_NODE_TOPK_MAX_K}]")
-    n = row_idx.numel()
-    n_seg = seg_ptr.numel() - 1
-    if n_seg < 1:
-        raise ValueError(f"{name}: seg_ptr must have n_seg + 1 >= 2 entries")
-    if seg_rel is not None and seg_rel.numel() != n_seg:
-        raise ValueError(f"{name}: seg_rel must have one entry per segment")
-    if n + 32 * n_seg >= 2**31:
-        raise ValueError(f"{name}: needs queries + 32·segments < 2^31")
-    if no_self and n_rows != n_cols:
-        raise ValueError(f"{name}: no_self needs square tables")
-    ks = set() if ops.K is None else {ops.K}  # … and the exclusion's relation count
-    ex_rowptr, ex_col = _stacked_exclusion(name, exclude, n_rows, n_cols, ks)
-    if len(ks) > 1:
-        raise ValueError(f"{name}: relation counts disagree: {sorted(ks)}")
-    K = ks.pop() if ks else None
-    if K is not None and K < 1:
-        raise ValueError(f"{name}: no relations")
-    if seg_rel is None and K is not None and n_seg > K:
-        raise ValueError(f"{name}: {n_seg} segments but {K} relations (pass seg_rel)")
-    _need_device(list(ops.tabs) + idx)
-    dev = G.device
-    if ex_rowptr is not None:
-        ex_rowptr, ex_col = _exclusion_on_device(name, ex_rowptr, ex_col, K, n_rows, dev)
+    d, n_rows, n_cols, dev = ops.d, ops.n_rows, ops.n_cols, G.device
     lib = _lib.load()
     nbytes = int(lib.dg_decoder_node_topk_workspace(n, n_seg, n_cols, topk))
     ws = torch.empty(-(-nbytes // 16) * 2, dtype=torch.int64, device=dev) if nbytes else None
@@ -1456,7 +1449,7 @@ def decoder_node_topk(row_table: torch.Tensor, col_table: torch.Tensor, row_idx:
         col_table=col_table.data_ptr(), ld_col=d, n_cols=n_cols, row_idx=row_idx.data_ptr() if n else None,
         seg_ptr=seg_ptr.data_ptr(), seg_rel=seg_rel.data_ptr() if seg_rel is not None else None, n_seg=n_seg,
         n_queries=n, **dict(zip(("G", "g_stride", "l", "l_stride"), ops.c_args())),
-        n_rel=K if K is not None else ops.n_rel(n_seg, seg_rel is not None), d=d, topk=topk,
+        n_rel=n_rel, d=d, topk=topk,
         excl_rowptr=ex_rowptr.data_ptr() if ex_rowptr is not None else None,
         excl_col=ex_col.data_ptr() if ex_col is not None else None, flags=flags,
         out_score=scores.data_ptr() if n else None, out_col=cols.data_ptr() if n else None,
